@@ -6,17 +6,21 @@ on the synthetic PDE-control-like equality QP  n = 1e6, m = 1e5, nnz(A) = 1e7, f
 user-model f, g, c  +  solve_two_mixed (the two KKT solves)  +  the ys/gs epilogue  +  Hsv  +  rho A'c.
 Inputs (A, q, d, b and all evaluation points) are resident in HBM before the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a torch.distributed environment: bench.py starts the N ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, before anything touches the GPU) and relays rank 0's
-line; under the driver's own torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.  The K-step timed pass
-(barrier + synchronize on both sides, max over ranks) is repeated R times (>= 1 s in total); `ms_per_step` / `value`
-are the MEDIAN pass, min / max are reported next to them.
+line; under the driver's own torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.  A plain run sets up, runs W
+warm-up steps and times exactly K steps in one pass (barrier + synchronize on both sides, max over ranks): `ms_per_step`
+/ `value` are that pass.  --dump-outputs DIR then writes what the last timed step returned to its caller as
+DIR/<name>.npy (float64; the inputs are seeded, so two builds can be compared output for output).
 
-Prints ONE JSON line on rank 0 (contract in the task brief) with `roofline` (dominant kernel = the SpMV/SpMM product
-kernels, algorithmic bytes / per-launch HIP-event time, measured live in a second pass) and `cpu_baseline` (the
-single-threaded C restatement of the reference's iterative path, oracle/fps_oracle.c, on a bounded sample).
+Prints ONE JSON line on rank 0 (metric, value, unit, ms_per_step, higher_is_better, dtype, config, ...).  --full adds
+everything that is not the headline: the K-step pass is repeated R times (>= 1 s in total; `ms_per_step` / `value` are
+then the MEDIAN pass, min / max next to them), `roofline` (dominant kernel = the SpMV/SpMM product kernels, algorithmic
+bytes / per-launch HIP-event time, measured live in a second pass), `cpu_baseline` (the single-threaded C restatement of
+the reference's iterative path, oracle/fps_oracle.c, on a bounded sample, and its OpenMP build) and, for a sharded N > 1
+run, `replicas_alternative`.
 """
 import argparse
 import json
@@ -46,8 +50,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=0,
-                    help="timed K-step passes (0 = as many as make >= 1 s of timed work, 3..50); median reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed K-step passes (0 = as many as make >= 1 s of timed work, 3..50); median reported.  "
+                         "Default: 1, with --full 0")
+    ap.add_argument("--full", action="store_true", default=False,
+                    help="also measure what is not the headline: repeated passes (see --repeats), the roofline pass, "
+                         "the CPU baselines (--cpu-evals) and, sharded with N > 1, the replicas alternative")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy")
     ap.add_argument("--workload", default=WORKLOADS[0], choices=WORKLOADS)
     ap.add_argument("--op", default="objgrad", choices=["objgrad", "hprod-solves", "hprod", "extras"],
                     help="objgrad = the headline metric; hprod-solves = solve_two_least_squares (the two solves of every "
@@ -70,7 +80,7 @@ def parse_args():
                          "K = [I A'; A -delta I] itself (fpsq_options.kkt_method = FPSQ_KKT_MINRES_K; named by "
                          "BASELINE.json's north_star / configs[1], not a path of the reference) -- with --op hprod-solves")
     ap.add_argument("--lookahead", type=int, default=0, help="override fpsq_options.lookahead (0 = library default)")
-    ap.add_argument("--cpu-evals", type=int, default=6, help="evaluations timed for cpu_baseline (0 = skip)")
+    ap.add_argument("--cpu-evals", type=int, default=6, help="--full: evaluations timed for cpu_baseline (0 = skip)")
     ap.add_argument("--pointers", default="device", choices=["device", "host", "host+jac", "device+jac"],
                     help="device: x / gx resident in HBM (the `value` of the contract).  host: x and gx are host arrays "
                          "(PCIe inside the timed region: what a Julia caller holding host vectors gets).  host+jac: "
@@ -94,8 +104,11 @@ def parse_args():
     ap.add_argument("--force-shard", action="store_true", default=False,
                     help="rehearsal on one GPU: run the sharded code path (RCCL communicator of size 1)")
     ap.add_argument("--no-roofline-pass", action="store_true", default=False,
-                    help="skip the second (per-launch HIP event) pass -- for runs under rocprofv3")
-    return ap.parse_args()
+                    help="--full: skip the second (per-launch HIP event) pass -- for runs under rocprofv3")
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 0 if args.full else 1
+    return args
 
 
 def self_launch(args) -> int:
@@ -117,6 +130,16 @@ def product_bytes(n, m, nnz, nrhs):
     a = 12 * nnz + 4 * (m + 1) + 8 * nrhs * (n + 2 * m)   # y(m) = ca * A x(n) + cb * y(m)
     at = 12 * nnz + 4 * (n + 1) + 8 * nrhs * (m + 2 * n)  # y(n) = ca * A'x(m) + cb * y(n)
     return a, at
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per output (host copy, float64).  Every workload's outputs fit the 64 MB budget
+    whole (the largest, --op hprod-solves at the headline size, is 17.6 MB), so nothing is sampled."""
+    host = {k: np.atleast_1d(np.asarray(v.cpu() if hasattr(v, "cpu") else v, dtype=np.float64)) for k, v in arrays.items()}
+    assert sum(a.nbytes for a in host.values()) <= 64 << 20, {k: a.nbytes for k, a in host.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def make_workload(name):
@@ -155,6 +178,7 @@ class Timer:
         return v
 
     def run(self, step, W, K, repeats, collect=None, warmed=False):
+        """Returns the pass times; self.last = what the last timed step returned."""
         for t in range(0 if warmed else W):
             step(t)
         times = []
@@ -168,6 +192,7 @@ class Timer:
                 if collect is not None and r == 0:
                     collect(out)
             self.barrier()
+            self.last = out
             times.append(self.maxreduce(time.perf_counter() - t0))
             if r == 0 and repeats <= 0:  # as many passes as make >= 1 s of timed work (same count on every rank)
                 R = int(min(50, max(3, np.ceil(1.0 / max(times[0], 1e-6)))))
@@ -197,16 +222,18 @@ def bench_dense(args, rank, world, local_rank, timer, dev):
     tsum = np.zeros(3)
 
     def step(t):
-        fp.objgrad(xs[t])
+        fx, gx = fp.objgrad(xs[t])
         assert qds.factorized
         i = qds.info()
-        return np.array([i["last_syrk_ms"], i["last_chol_ms"], i["last_solve_ms"]])
+        return np.array([i["last_syrk_ms"], i["last_chol_ms"], i["last_solve_ms"]]), fx, gx
 
     def collect(v):
-        tsum.__iadd__(v)
+        tsum.__iadd__(v[0])
 
     torch.cuda.synchronize()
     times = timer.run(step, W, K, args.repeats, collect)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"fx": timer.last[1], "gx": timer.last[2]})
     med = float(np.median(times))
     # algorithmic flops of one step: SYRK m^2 n (lower triangle of the Gram matrix, 2 flops per multiply-add pair
     # counted on half the entries), Cholesky m^3 / 3, two triangular solves x two right-hand sides 4 m^2,
@@ -233,7 +260,7 @@ def bench_dense(args, rank, world, local_rank, timer, dev):
                                       "solve": round(dev_ms[2], 4)},
                         "syrk_tflops": round(1.0 * m * m * n / (dev_ms[0] * 1e-3) / 1e12, 2),
                         "cholesky_tflops": round(m ** 3 / 3.0 / (dev_ms[1] * 1e-3) / 1e12, 2)}}
-    if rank == 0 and world == 1 and args.cpu_evals > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_evals > 0:
         import scipy.linalg as sla
 
         Ad = qp.scipy_csr().toarray()
@@ -394,7 +421,7 @@ def main():
     # ---- N > 1, sharded: FIRST the same ranks as independent replicas (no data-path collective) -- a second number for
     # the record (`replicas_alternative`), never the `value` of a sharded run
     replicas_alt = None
-    if sharded and world > 1 and args.op == "objgrad":
+    if args.full and sharded and world > 1 and args.op == "objgrad":
         _, rep = build_model("replicas")
         K0, W0 = args.steps, args.warmup
         xs0 = torch.empty((K0 + W0, n), dtype=torch.float64, device=dev)
@@ -542,10 +569,16 @@ def main():
     med = float(np.median(times))
     evals = K if sharded else K * world  # sharded: all ranks work on the same K evaluations
     value = evals / med
+    if rank == 0 and args.dump_outputs:  # (sharded: rank 0's window of grad(phi))
+        dump_outputs(args.dump_outputs,
+                     {"Hv": hp_out[0]} if hfull
+                     else {"out1": hp_out[1], "out2": hp_out[3]} if extras
+                     else dict(zip(("p1", "q1", "p2", "q2"), hp_out)) if hp
+                     else {"fx": timer.last[0], "gx": gx})
 
     # ---- roofline of the dominant kernel: a second pass over the same K points with per-launch HIP events
     roofline = None
-    if not args.no_roofline_pass and not extras and not (hfull and args.hessian_approx == 1) and not args.alternate_delta:  # (timing only for those)
+    if args.full and not args.no_roofline_pass and not extras and not (hfull and args.hessian_approx == 1) and not args.alternate_delta:  # (timing only for those)
         model.set_profiling(True)
         pa, pat, t_ms, tot_ms, nfused, nmulti_saved = np.zeros(2), np.zeros(2), 0.0, 0.0, 0, 0
         for t in range(W, W + K):
@@ -704,7 +737,7 @@ def main():
         out["replicas_alternative"] = replicas_alt
 
     # ---- CPU baseline: the C restatement of the reference's iterative path, one thread, bounded sample
-    if rank == 0 and world == 1 and args.cpu_evals > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_evals > 0:
         from oracle import oracle
 
         oracle.build()

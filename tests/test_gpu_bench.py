@@ -20,7 +20,7 @@ def _run(args, env=None, timeout=600):
 
 
 def test_bench_prints_one_contract_line():
-    r = _run(SMALL + ["--cpu-evals", "1"])
+    r = _run(SMALL + ["--full", "--cpu-evals", "1"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -32,6 +32,31 @@ def test_bench_prints_one_contract_line():
     assert d["roofline"]["bound"] == "hbm" and 0.0 < d["roofline"]["frac"] <= 1.0
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1
     assert "workload" in d["config"] and "model" not in d["config"]
+
+
+def test_plain_run_times_its_steps_once_and_dumps_the_last_step(tmp_path, oracle):
+    """Without --full: ONE pass of exactly --steps timed steps and none of the extras.  --dump-outputs writes what the last
+    timed step returned to its caller: phi and grad(phi) at step t = W + K - 1, i.e. at the seeded point 1 + t."""
+    import numpy as np
+
+    import fps_amd  # noqa: F401
+    from fps_amd import problems
+
+    out = tmp_path / "outputs"
+    r = _run(["--workload", "random-eqqp n=1e5 m=1e4 nnz=1e6", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["repeats"] == 1 and d["ms_per_step"] > 0
+    assert d["roofline"] is None and "cpu_baseline" not in d
+    assert sorted(os.listdir(out)) == ["fx.npy", "gx.npy"]
+    fx, gx = np.load(out / "fx.npy"), np.load(out / "gx.npy")
+    qp = problems.random_eqqp(n=100_000, m=10_000)
+    assert fx.dtype == gx.dtype == np.float64 and fx.shape == (1,) and gx.shape == (qp.n,)
+    ref = oracle.qp_objgrad(qp, qp.point(1 + 3), 1e3, 1.0, 0.0)
+    assert np.max(np.abs(gx - ref["gx"])) < 1e-8 * np.max(np.abs(ref["gx"]))
+    assert abs(fx[0] - ref["fx"]) <= 1e-8 * abs(ref["fx"])
 
 
 def test_force_shard_world1_runs_the_sharded_path_through_rccl():
@@ -85,7 +110,7 @@ def test_multi_rank_sharded_bench_runs_through_the_loopback_collectives(ranks):
     every evaluation solved, and the iteration counts of the single-GPU run of the same points."""
     env = {"FPSQ_BENCH_REHEARSE": "1", "FPSQ_RCCL_LIB": _shim(), "FPSQ_BENCH_WATCHDOG": "400", "FPSQ_SHIM_TIMEOUT": "120"}
     r = _run(["--gpus", str(ranks), "--parallel", "shard", "--steps", "2", "--warmup", "1", "--repeats", "1", "--cpu-evals", "0",
-              "--no-roofline-pass"], env=env, timeout=900)
+              "--no-roofline-pass", "--full"], env=env, timeout=900)
     if r.returncode != 0:
         # pytest shortens the assertion's text: what the ranks said goes into the REPORT ITSELF (captured output of a failed
         # test is printed in full) -- a side file under gpurun_out/ does not come back from the driver's run

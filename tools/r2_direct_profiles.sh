@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r2prof
 mkdir -p $O
-timeout -k 10 250 python bench.py --workload "dense-block n=4096 m=2048" --steps 10 --warmup 2 > $O/bench_dense_block.json 2>> $O/err.log; echo "dense rc=$?"
+timeout -k 10 250 python bench.py --full --workload "dense-block n=4096 m=2048" --steps 10 --warmup 2 > $O/bench_dense_block.json 2>> $O/err.log; echo "dense rc=$?"
 rm -rf $O/dks; timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/dks -o d -- python3 bench.py --workload "dense-block n=4096 m=2048" --steps 5 --warmup 1 --cpu-evals 0 --repeats 1 > $O/dks.log 2>&1; echo "dense stats rc=$?"
 rm -rf $O/bks; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bks -o b -- python3 tools/band_headline.py > $O/band_headline_prof.txt 2>&1; echo "band stats rc=$?"
 timeout -k 10 200 python tools/band_headline.py > $O/band_headline.txt 2>&1; echo "band rc=$?"

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r2prof
 mkdir -p $O
-B="timeout -k 10 250 python bench.py"
+B="timeout -k 10 250 python bench.py --full"
 $B > $O/bench_headline.json 2> $O/err.log; echo "headline rc=$?"
 $B --delta 1.4901161193847656e-08 --cpu-evals 0 > $O/bench_headline_delta_sqrteps.json 2>> $O/err.log; echo "delta rc=$?"
 $B --workload "random-eqqp n=1e5 m=1e4 nnz=1e6" --cpu-evals 2 > $O/bench_cfg2.json 2>> $O/err.log; echo "cfg2 rc=$?"
@@ -15,7 +15,7 @@ $B --op extras --cpu-evals 0 > $O/bench_extras.json 2>> $O/err.log; echo "extras
 $B --pointers host --cpu-evals 0 > $O/bench_host_pointers.json 2>> $O/err.log; echo "host rc=$?"
 $B --pointers host+jac --cpu-evals 0 > $O/bench_host_pointers_jac.json 2>> $O/err.log; echo "host+jac rc=$?"
 $B --force-shard --cpu-evals 0 > $O/bench_force_shard_world1.json 2>> $O/err.log; echo "force-shard rc=$?"
-rm -rf $O/ks; timeout -k 10 250 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o k -- python3 bench.py --steps 20 --warmup 3 --cpu-evals 0 --repeats 2 > $O/ks.log 2>&1; echo "kernel stats rc=$?"
+rm -rf $O/ks; timeout -k 10 250 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o k -- python3 bench.py --full --steps 20 --warmup 3 --cpu-evals 0 --repeats 2 > $O/ks.log 2>&1; echo "kernel stats rc=$?"
 python3 tools/timeline.py $O/ks/k_kernel_trace.csv > $O/timeline.txt 2>&1
 rm -rf $O/pf; timeout -k 10 250 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pf -o f -- python3 bench.py --steps 2 --warmup 1 --cpu-evals 0 --repeats 1 --no-roofline-pass > $O/pf.log 2>&1; echo "pmc fetch rc=$?"
 rm -rf $O/pw; timeout -k 10 250 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pw -o w -- python3 bench.py --steps 2 --warmup 1 --cpu-evals 0 --repeats 1 --no-roofline-pass > $O/pw.log 2>&1; echo "pmc write rc=$?"

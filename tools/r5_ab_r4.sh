@@ -1,7 +1,7 @@
 # developer script (GPU box): this tree's library against round 4's final one (946e069, built into gpurun_ab_libfpsq_r4.so),
 # interleaved on one box
 mkdir -p gpurun_out/r5
-B="timeout -k 10 200 python bench.py --cpu-evals 0 --workload"
+B="timeout -k 10 200 python bench.py --full --cpu-evals 0 --workload"
 W="pde-control-like n=1e6 m=1e5 nnz=1e7"
 for r in 1 2 3; do
   FPSQ_LIB_PATH=$PWD/gpurun_ab_libfpsq_r4.so $B "$W" > gpurun_out/r5/abr4_old_$r.json 2> gpurun_out/r5/abr4_old_$r.err; echo "old $r rc=$?"

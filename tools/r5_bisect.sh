@@ -1,6 +1,6 @@
 # developer script (GPU box): where did k_iter_fused get slower?  in-run product-launch averages of libraries built at this round's commits
 mkdir -p gpurun_out/r5
-B="timeout -k 10 200 python bench.py --cpu-evals 0 --repeats 20 --workload"
+B="timeout -k 10 200 python bench.py --full --cpu-evals 0 --repeats 20 --workload"
 W="pde-control-like n=1e6 m=1e5 nnz=1e7"
 for r in 1 2; do
   for c in r4 cur; do

@@ -1,6 +1,6 @@
 # developer script (GPU box): cfg2 (n = 1e5, m = 1e4, random columns) -- two launches per iteration (default) / one / several iterations per launch
 mkdir -p gpurun_out/r5
-B="timeout -k 10 200 python bench.py --cpu-evals 0 --workload"
+B="timeout -k 10 200 python bench.py --full --cpu-evals 0 --workload"
 W="random-eqqp n=1e5 m=1e4 nnz=1e6"
 for r in 1 2; do
   $B "$W" > gpurun_out/r5/c2_def_$r.json 2> gpurun_out/r5/c2_def_$r.err; echo "default $r rc=$?"

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r5prof
 mkdir -p $O
-B="timeout -k 10 200 python bench.py"
+B="timeout -k 10 200 python bench.py --full"
 # the traffic passes FIRST: the bench lines below then find a profile of THESE kernel sources (bench.py refuses any other) -- the
 # box has no .git, so the caller passes the commit: FPSQ_GIT_HEAD=$(git rev-parse --short HEAD) in front of the gpurun command
 rm -rf $O/pf; timeout -k 10 150 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pf -o f -- python3 bench.py --steps 2 --warmup 1 --cpu-evals 0 --repeats 1 --no-roofline-pass > $O/pf.log 2>&1; echo "pmc fetch rc=$?"
@@ -23,9 +23,9 @@ $B --op hprod --cpu-evals 0 > $O/bench_hprod.json 2>> $O/err.log; echo "hprod rc
 $B --op hprod --hessian-approx 1 --cpu-evals 0 > $O/bench_hprod_val1.json 2>> $O/err.log; echo "hprod val1 rc=$?"
 $B --op extras --cpu-evals 0 > $O/bench_extras.json 2>> $O/err.log; echo "extras rc=$?"
 $B --pointers device+jac --cpu-evals 0 > $O/bench_device_pointers_jac.json 2>> $O/err.log; echo "device+jac rc=$?"
-rm -rf $O/ks; timeout -k 10 150 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o k -- python3 bench.py --steps 20 --warmup 3 --cpu-evals 0 --repeats 2 > $O/ks.log 2>&1; echo "kernel stats rc=$?"
+rm -rf $O/ks; timeout -k 10 150 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o k -- python3 bench.py --full --steps 20 --warmup 3 --cpu-evals 0 --repeats 2 > $O/ks.log 2>&1; echo "kernel stats rc=$?"
 python3 tools/timeline.py $O/ks/k_kernel_trace.csv k_startup > $O/timeline.txt 2>&1
-rm -rf $O/ksf; timeout -k 10 150 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ksf -o k -- python3 bench.py --steps 20 --warmup 3 --cpu-evals 0 --repeats 2 --force-shard > $O/ksf.log 2>&1; echo "kernel stats force-shard rc=$?"
+rm -rf $O/ksf; timeout -k 10 150 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ksf -o k -- python3 bench.py --full --steps 20 --warmup 3 --cpu-evals 0 --repeats 2 --force-shard > $O/ksf.log 2>&1; echo "kernel stats force-shard rc=$?"
 python3 tools/timeline.py $O/ksf/k_kernel_trace.csv k_startup > $O/timeline_force_shard.txt 2>&1
 # SQ / TCP counters of the FINAL loop kernel (k_iter_fused): separate --pmc passes, --kernel-trace only
 rm -f $O/pmc_sq.txt
