@@ -847,8 +847,6 @@ struct fpsq_solver_s {
   // developer probe (FPSQ_FUSE_PROBE=<file>, FPSQ_FUSE_PROBE_AT=<n-th fused launch of the handle>): per-workgroup time stamps of one launch
   int64_t fuse_probe_at = 0;
   bool fuse_tail = true;               // FPSQ_FUSE_TAIL=0: the raw A'[q1, c] product and k_qp_penalty_grad as two launches (one GPU; bitwise the same)
-  const GradEpi* tail_grad = nullptr;  // set around the tail's product launch: launch_spmv then picks k_spmv<.., GRAD>
-  bool tail_grad_used = false;         // ... and says so (a layout it has no GRAD variant for: the caller launches k_qp_penalty_grad)
   unsigned long long* fuse_probe_buf = nullptr;
   int fuse_probe_grid = 0;
   std::vector<int> fuse_probe_layout;
@@ -908,10 +906,6 @@ struct fpsq_solver_s {
   MinresState* mk_state = nullptr;  // [2]
   double* mk_part[2] = {nullptr, nullptr};
   int mk_gl = 0, mk_gs = 0;
-  // Speculative epilogue (run_krylov): kernels launched while gate0 is set only act once BOTH lane controls say `done`.
-  const LaneCtl* gate0 = nullptr;
-  const LaneCtl* gate1 = nullptr;
-  bool tail_was_run = false;   // the caller's epilogue was enqueued (gated) inside run_krylov and the gates were open
   int64_t expect_iters[5][5][2] = {};  // [kind of lane 0][kind of lane NL-1]: iterations the last two such runs needed
   bool adaptive_runahead = true;    // FPSQ_ADAPTIVE_RUNAHEAD=0 disables (A/B)
   // FPSQ_HOST_TRACE=1: host timestamps at fixed points of fpsq_qp_objgrad, averaged and printed at destroy (developer aid)
@@ -920,12 +914,6 @@ struct fpsq_solver_s {
   int64_t ht_calls = 0;
   std::chrono::steady_clock::time_point ht_last, ht_exit;
   bool ht_have_exit = false;
-  // start-up launch of the next run also evaluates the eq-QP gradient (qp_objgrad's fast start): nblk > 0
-  QpGradArgs startup_qg{};
-  // The final LSQR x update may be left to the caller's epilogue when its FIRST kernel is k_ys (absorb_flush, set by
-  // qp_objgrad): run_krylov then parks the segment here instead of launching it.
-  bool absorb_flush = false;
-  UpdSeg pending_flush{};
   // stream-ordered outputs (fpsq_set_output_ordering)
   bool out_ordered = false;
   hipEvent_t ev_out = nullptr;
@@ -1496,6 +1484,11 @@ inline bool insum(fpsq_handle h) {
 // ... and when other ranks exist: the table the kernels are given (null: one GPU, or a communicator of one)
 inline const XchTable* insum_table(fpsq_handle h) { return h->comm && h->comm->nranks > 1 ? h->comm->xch_table() : nullptr; }
 inline int64_t n_owned(fpsq_handle h) { return h->halo ? h->n - h->ovr : h->n; }
+// the number of the next in-launch sum over the ranks (0 means "no exchange" to the kernels: skipped when the counter wraps)
+inline uint32_t next_xseq(fpsq_handle h) {
+  if (++h->xch_seq == 0) ++h->xch_seq;
+  return h->xch_seq;
+}
 
 int alloc_workspaces(fpsq_handle h) {
   const size_t n = (size_t)h->n, m = (size_t)h->m;
@@ -1727,6 +1720,14 @@ UpdSeg seg_none() {
   return s;
 }
 
+GradEpi grad_none() { return GradEpi{}; }
+
+// Speculative epilogue (run_krylov): kernels launched with gates only act once BOTH lane controls say `done` (none: always)
+struct Gates {
+  const LaneCtl* c0 = nullptr;
+  const LaneCtl* c1 = nullptr;
+};
+
 // u0/u1: vector-update segments that ride in the product launch (run_fused_updates); they may only read what the
 // product reads.
 // halo_rows (A' products of a halo-mode handle): the overlap rows of the rank's column window only get their raw sums,
@@ -1736,7 +1737,7 @@ UpdSeg seg_none() {
 template <int NL>
 void launch_spmv(fpsq_handle h, int tag, const double* x, const double* yin, double* yout, const LaneCtl* c0,
                  const LaneCtl* c1, double* partials, const UpdSeg& u0 = seg_none(), const UpdSeg& u1 = seg_none(),
-                 bool halo_rows = false, const StepArgs* pre = nullptr) {
+                 bool halo_rows = false, const StepArgs* pre = nullptr, Gates gates = {}) {
   const int nupd = u0.nblk + u1.nblk;
   const HaloRows hr{h->ovl, h->n - h->ovr, h->halo_raw};
   StepArgs z0{}, z1{};
@@ -1760,7 +1761,7 @@ void launch_spmv(fpsq_handle h, int tag, const double* x, const double* yin, dou
     const int per_xcd = (h->RA.view.ng + 7) / 8;
 #define FPSQ_LAUNCH_RGCS(...) \
     launch_product(h, k_spmv_rgcs<__VA_ARGS__>, dim3(per_xcd * 8 + nupd + (lead ? kRideCand : 0)), h->RA.view, x, yin, yout, c0, c1, partials, \
-                   per_xcd, u0, u1, h->gate0, h->gate1, h->strA, z0, z1, ra)
+                   per_xcd, u0, u1, gates.c0, gates.c1, h->strA, z0, z1, ra)
     if constexpr (NL == 2) {
       // (a sharded handle whose leaders form their sums over the ranks in the launch: the variants with the exchange compiled in)
       if (lead && ra.xt != nullptr && h->RA.view.stride) FPSQ_LAUNCH_RGCS(2, true, true, true);
@@ -1776,13 +1777,11 @@ void launch_spmv(fpsq_handle h, int tag, const double* x, const double* yin, dou
   } else {
     const DevCsr& M = tag == TAG_A ? h->A : h->AT;
     const int per_xcd = (M.nblk + 7) / 8;
-    // the tail of a call on one GPU: the raw product's rows go straight into the call's result (grad(phi): two lanes; Hv: one)
-    const bool grad = h->tail_grad != nullptr && tag == TAG_AT && !lead && !halo_rows && M.sorted && nupd == 0;
-    const GradEpi ge = grad ? *h->tail_grad : GradEpi{};
-    const dim3 grid(per_xcd * 8 + nupd + (grad && ge.fx.out != nullptr ? 1 : 0));
+    const dim3 grid(per_xcd * 8 + nupd);
     const int ps = tag == TAG_A ? h->strA : h->strT;
 #define FPSQ_LAUNCH_SPMV(...) \
-    launch_product(h, k_spmv<__VA_ARGS__>, grid, M.view(), x, yin, yout, c0, c1, partials, per_xcd, u0, u1, h->gate0, h->gate1, ps, hr, ge)
+    launch_product(h, k_spmv<__VA_ARGS__>, grid, M.view(), x, yin, yout, c0, c1, partials, per_xcd, u0, u1, gates.c0, gates.c1, ps, hr, \
+                   grad_none())
     bool done_pre = false;
     if constexpr (NL == 2) {
       if (lead) {  // (tag == TAG_AT: padded blocks with block-relative columns)
@@ -1818,9 +1817,6 @@ void launch_spmv(fpsq_handle h, int tag, const double* x, const double* yin, dou
       else if (M.col16) FPSQ_LAUNCH_SPMV(NL, TAG_AT, true, false, true);
       else if (M.padded) FPSQ_LAUNCH_SPMV(NL, TAG_AT, false, true, true);
       else FPSQ_LAUNCH_SPMV(NL, TAG_AT, false, false, true);
-    } else if (grad) {
-      FPSQ_LAUNCH_SPMV(NL, TAG_AT, true, true, false, true, true);
-      h->tail_grad_used = true;
     } else if (M.sorted) FPSQ_LAUNCH_SPMV(NL, TAG_AT, true, true, false, true);
     else if (M.col16 && M.padded) FPSQ_LAUNCH_SPMV(NL, TAG_AT, true, true);
     else if (M.col16) FPSQ_LAUNCH_SPMV(NL, TAG_AT, true);
@@ -1831,6 +1827,30 @@ void launch_spmv(fpsq_handle h, int tag, const double* x, const double* yin, dou
   h->launches++;
   h->spmv_launches++;
   (tag == TAG_A ? h->prod_a : h->prod_at)[NL - 1]++;
+}
+
+// The tail of a call runs as on one GPU: no communicator, or one of ONE rank (no overlap rows, no peers: its products need no
+// sum over the ranks), and an A' layout with a GRAD variant
+inline bool single_gpu_tail(fpsq_handle h) {
+  return h->fuse_tail && (!h->comm || (h->comm->nranks == 1 && h->ovl + h->ovr == 0)) && h->AT.sorted && h->AT.padded;
+}
+
+// The tail's raw A' product on one GPU: its rows go straight into the call's result (k_spmv<.., GRAD>; grad(phi): two lanes,
+// Hv: one).  False: the layout has no GRAD variant, nothing was launched (the caller launches the product and the kernel that
+// combines its rows).
+template <int NL>
+bool launch_at_tail(fpsq_handle h, const double* x, double* yout, const GradEpi& ge, Gates gates = {}) {
+  const DevCsr& M = h->AT;
+  if (!M.sorted) return false;
+  const int per_xcd = (M.nblk + 7) / 8;
+  const HaloRows hr{h->ovl, h->n - h->ovr, h->halo_raw};
+  launch_product(h, k_spmv<NL, TAG_AT, true, true, false, true, true>, dim3(per_xcd * 8 + (ge.fx.out != nullptr ? 1 : 0)), M.view(),
+                 x, (const double*)nullptr, yout, h->ctl_raw, h->ctl_raw, (double*)nullptr, per_xcd,
+                 seg_none(), seg_none(), gates.c0, gates.c1, h->strT, hr, ge);
+  h->launches++;
+  h->spmv_launches++;
+  h->prod_at[NL - 1]++;
+  return true;
 }
 
 __global__ void k_set_ctl(LaneCtl* c, double ca, double cb) {
@@ -1853,9 +1873,10 @@ const LaneCtl* const_ctl(fpsq_handle h, double ca, double cb) {
 }
 
 // out = ca * op(A) x + cb * yin with host-given constants
-void spmv_const(fpsq_handle h, int tag, double ca, const double* x, double cb, const double* yin, double* yout) {
+void spmv_const(fpsq_handle h, int tag, double ca, const double* x, double cb, const double* yin, double* yout,
+                Gates gates = {}) {
   const LaneCtl* c = const_ctl(h, ca, cb);
-  launch_spmv<1>(h, tag, x, yin, yout, c, c, nullptr);
+  launch_spmv<1>(h, tag, x, yin, yout, c, c, nullptr, seg_none(), seg_none(), false, nullptr, gates);
 }
 
 int comm_allreduce(fpsq_handle h, double* buf, size_t count) {
@@ -1875,13 +1896,14 @@ int comm_reduce_long(fpsq_handle h, double* buf, int NL) { return comm_allreduce
 // Halo mode, after k_spmv<.., HALO>: exchange the raw sums of the two overlap regions with the neighbours, then finish
 // those rows (yout = ca (own + neighbour's) + cb yin, squared-norm partials of the owned head region behind the product's).
 template <int NL>
-int halo_finish(fpsq_handle h, const double* yin, double* yout, const LaneCtl* c0, const LaneCtl* c1, double* partials) {
+int halo_finish(fpsq_handle h, const double* yin, double* yout, const LaneCtl* c0, const LaneCtl* c1, double* partials,
+                Gates gates = {}) {
   const int64_t t = h->ovl + h->ovr;
   if (t == 0) return 0;
   double* rl = h->halo_recv + (size_t)(h->halo_calls++ & 1) * (size_t)t * 2;
   {  // peer-to-peer routes: exchange + finish in one launch
     const HaloFinishArgs fa{h->halo_raw, rl, h->ovl, h->ovr, h->n - h->ovr, yin, yout, c0, c1,
-                            partials ? partials + h->AT.nblk : nullptr, h->strT, 0 /* dbg: the route's */, h->gate0, h->gate1};
+                            partials ? partials + h->AT.nblk : nullptr, h->strT, 0 /* dbg: the route's */, gates.c0, gates.c1};
     if (h->comm->halo_exchange_finish(NL, fa, h->halo_gf, h->stream)) {
       h->launches++;
       return 0;
@@ -1892,32 +1914,33 @@ int halo_finish(fpsq_handle h, const double* yin, double* yout, const LaneCtl* c
     return rc;
   }
   hipLaunchKernelGGL(k_halo_finish<NL>, dim3(h->halo_gf), dim3(kBlock), 0, h->stream, h->halo_raw, rl, h->ovl,
-                     h->ovr, h->n - h->ovr, yin, yout, c0, c1, partials ? partials + h->AT.nblk : nullptr, h->strT, h->gate0,
-                     h->gate1);
+                     h->ovr, h->n - h->ovr, yin, yout, c0, c1, partials ? partials + h->AT.nblk : nullptr, h->strT, gates.c0,
+                     gates.c1);
   h->launches++;
   return 0;
 }
 
 template <int NL>
 int at_product(fpsq_handle h, const double* x, double* y, const LaneCtl* c0, const LaneCtl* c1, double* partials,
-               int* np, const UpdSeg& u0 = seg_none(), const UpdSeg& u1 = seg_none(), const StepArgs* pre = nullptr) {
+               int* np, const UpdSeg& u0 = seg_none(), const UpdSeg& u1 = seg_none(), const StepArgs* pre = nullptr,
+               Gates gates = {}) {
   if (!h->comm) {
-    launch_spmv<NL>(h, TAG_AT, x, y, y, c0, c1, partials, u0, u1, false, pre);
+    launch_spmv<NL>(h, TAG_AT, x, y, y, c0, c1, partials, u0, u1, false, pre, gates);
     *np = h->AT.nblk;
     return 0;
   }
   if (h->halo) {
     // every row the rank alone contributes to is finished by the product kernel exactly as on one GPU (so the vector
     // updates may ride in the launch); only the overlap rows wait for the neighbours
-    launch_spmv<NL>(h, TAG_AT, x, y, y, c0, c1, partials, u0, u1, /*halo_rows=*/true, pre);
+    launch_spmv<NL>(h, TAG_AT, x, y, y, c0, c1, partials, u0, u1, /*halo_rows=*/true, pre, gates);
     // (steps riding in that launch: the control blocks k_halo_finish must read are the ones the leaders have just written)
     const LaneCtl* f0 = pre ? reinterpret_cast<const LaneCtl*>(pre[0].state_out) : c0;
     const LaneCtl* f1 = pre ? reinterpret_cast<const LaneCtl*>(pre[NL - 1].state_out) : c1;
-    if (int rc = halo_finish<NL>(h, y, y, f0, f1, partials)) return rc;
+    if (int rc = halo_finish<NL>(h, y, y, f0, f1, partials, gates)) return rc;
     *np = h->AT.nblk + h->halo_gf;
     return 0;
   }
-  launch_spmv<NL>(h, TAG_AT, x, nullptr, h->comm_vec, h->ctl_raw, h->ctl_raw, nullptr);
+  launch_spmv<NL>(h, TAG_AT, x, nullptr, h->comm_vec, h->ctl_raw, h->ctl_raw, nullptr, seg_none(), seg_none(), false, nullptr, gates);
   if (int rc = comm_reduce_long(h, h->comm_vec, NL)) return rc;
   const int g = ew_grid(h->n);
   h->strT = g;  // replicated layout: the norm partials of the A' product come from this kernel, g per lane
@@ -1929,17 +1952,18 @@ int at_product(fpsq_handle h, const double* x, double* y, const LaneCtl* c0, con
 }
 
 // out = ca A' x + cb yin (plain vectors, host constants), all-reduced when sharded
-int at_product_const(fpsq_handle h, double ca, const double* x, double cb, const double* yin, double* yout) {
+int at_product_const(fpsq_handle h, double ca, const double* x, double cb, const double* yin, double* yout,
+                     Gates gates = {}) {
   if (!h->comm) {
-    spmv_const(h, TAG_AT, ca, x, cb, yin, yout);
+    spmv_const(h, TAG_AT, ca, x, cb, yin, yout, gates);
     return 0;
   }
   if (h->halo) {
     const LaneCtl* c = const_ctl(h, ca, cb);
-    launch_spmv<1>(h, TAG_AT, x, yin, yout, c, c, nullptr, seg_none(), seg_none(), /*halo_rows=*/true);
-    return halo_finish<1>(h, yin, yout, c, c, nullptr);
+    launch_spmv<1>(h, TAG_AT, x, yin, yout, c, c, nullptr, seg_none(), seg_none(), /*halo_rows=*/true, nullptr, gates);
+    return halo_finish<1>(h, yin, yout, c, c, nullptr, gates);
   }
-  launch_spmv<1>(h, TAG_AT, x, nullptr, h->comm_vec, h->ctl_raw, h->ctl_raw, nullptr);
+  launch_spmv<1>(h, TAG_AT, x, nullptr, h->comm_vec, h->ctl_raw, h->ctl_raw, nullptr, seg_none(), seg_none(), false, nullptr, gates);
   if (int rc = comm_reduce_long(h, h->comm_vec, 1)) return rc;
   hipLaunchKernelGGL(k_axpby_plain, dim3(ew_grid(h->n)), dim3(kBlock), 0, h->stream, h->comm_vec, ca, yin, cb, yout, h->n);
   h->launches++;
@@ -2223,7 +2247,7 @@ int prepare_step(fpsq_handle h, StepArgs& a0, StepArgs& a1, bool sharded = false
     // the step's workgroup forms the sum over the ranks itself (xch_sum): the arguments stay the rank's local arrays, and the pair
     // gets an exchange number -- the same sequence on every rank -- which travels next to the steps (h->last_xseq: the caller
     // hands it to k_step or to the launch whose leaders compute the pair).  A communicator of one: nothing at all.
-    if (insum_table(h) != nullptr && ((sh[0] && a0.kind != STEP_NONE) || (sh[1] && a1.kind != STEP_NONE))) h->last_xseq = ++h->xch_seq;
+    if (insum_table(h) != nullptr && ((sh[0] && a0.kind != STEP_NONE) || (sh[1] && a1.kind != STEP_NONE))) h->last_xseq = next_xseq(h);
     return 0;
   }
   if (h->comm && h->halo && (sh[0] || sh[1])) {
@@ -2313,17 +2337,35 @@ void launch_updates(fpsq_handle h, const UpdSeg& s0, const UpdSeg& s1, const Upd
 // other lane); running them side by side turns two SpMVs into one SpMM with k = 2.
 // `tail` (optional, single GPU): enqueues the caller's epilogue kernels.  When the iteration count of the previous call
 // of the same kind is known, the final LSQR flush and the tail are enqueued SPECULATIVELY right behind iteration
-// `expect`, gated on the lanes' `done` flags (h->gate0/1): if the recurrences do end there -- consecutive evaluations of
+// `expect`, gated on the lanes' `done` flags (TailCtx::gates): if the recurrences do end there -- consecutive evaluations of
 // a line search mostly repeat their counts -- the epilogue runs without the host first having to see `done` and only
 // then launching it (a ~30 us bubble per evaluation); if not, the gated kernels exit at once and the loop goes on.
-// h->tail_was_run tells the caller whether its epilogue has been taken care of.
+// RunResult::tail_was_run tells the caller whether its epilogue has been taken care of.
 //
 // Structure (round 4; one 640-line function before): KrylovRun::run() is the loop and knows three things -- a PRODUCT is
 // launched (with whatever rides in it), the STEPS behind it are posted (PendingSteps: they ride in the next product launch
 // or get a launch of their own), the host PACES itself (exchange boundaries of a sharded run, run-ahead, speculation).
 // What a recurrence of a given kind contributes at each of those points -- which step kinds, which update segments,
 // which partial arrays -- is in the builders (lane_*, *_seg, steps_after_*); nothing outside them switches on a lane's kind.
-using TailFn = std::function<int()>;
+struct TailCtx {
+  Gates gates;                // the speculative epilogue's gates (none: the epilogue runs after the loop)
+  UpdSeg flush = seg_none();  // the final LSQR x update, left to the epilogue's first kernel (k_ys; UPD_NONE: none)
+};
+using TailFn = std::function<int(const TailCtx&)>;
+
+// What the caller asks of one run beyond its lanes (qp_objgrad's fast start)
+struct RunRequest {
+  QpGradArgs startup_qg{};    // nblk > 0: the start-up launch of the run also evaluates the eq-QP gradient
+  // The final LSQR x update may be left to the caller's epilogue when its FIRST kernel is k_ys: the run then parks the
+  // segment in the TailCtx (or in RunResult::flush) instead of launching it.
+  bool absorb_flush = false;
+};
+
+// ... and what the caller needs from it afterwards
+struct RunResult {
+  bool tail_was_run = false;  // the caller's epilogue was enqueued (gated) inside the run and the gates were open
+  UpdSeg flush = seg_none();  // otherwise: the final LSQR x update the epilogue has to apply (absorb_flush)
+};
 
 // ---- what depends on the KIND of a recurrence
 inline int lane_begin_kind(const Lane& L) {
@@ -2357,6 +2399,8 @@ struct KrylovRun {
   fpsq_handle h;
   Lane* lanes;
   const TailFn* tail;
+  const RunRequest req;
+  RunResult res;
   const int64_t n, m;
   const fpsq_options& o;
   hipStream_t s;
@@ -2405,8 +2449,8 @@ struct KrylovRun {
   UpdSeg lu[2] = {seg_none(), seg_none()};  // what rides in (or precedes) this iteration's products: LSQR's update of the previous one
   int nlu = 0;
 
-  KrylovRun(fpsq_handle h_, Lane* lanes_, const TailFn* tail_)
-      : h(h_), lanes(lanes_), tail(tail_), n(h_->n), m(h_->m), o(h_->opt), s(h_->stream), gn(ew_grid(h_->n)), gm(ew_grid(h_->m)),
+  KrylovRun(fpsq_handle h_, Lane* lanes_, const TailFn* tail_, const RunRequest& req_)
+      : h(h_), lanes(lanes_), tail(tail_), req(req_), n(h_->n), m(h_->m), o(h_->opt), s(h_->stream), gn(ew_grid(h_->n)), gm(ew_grid(h_->m)),
         nbA(npart_A(h_)), LP(h_->LP), SP(h_->SP), expect_slot(h_->expect_iters[lanes_[0].kind][lanes_[NL - 1].kind]),
         local_vec(!h_->comm || h_->halo), SPcur(h_->SP), SPalt(h_->SP2) {
     none.kind = STEP_NONE;
@@ -2420,7 +2464,6 @@ struct KrylovRun {
 
   // ------------------------------------------------------------------ set-up of the lanes
   void setup() {
-    h->tail_was_run = false;
     // iteration count of the previous runs with the same pair of recurrences (0: unknown).  The scalar steps publish their
     // progress to the host only from that iteration on (and when a recurrence ends): see publish().
     // (sharded: only in halo mode, where every rank derives the same count from the replicated recurrence state)
@@ -2742,9 +2785,8 @@ struct KrylovRun {
       }
     }
     ht_mark(h, 3);
-    hipLaunchKernelGGL(k_startup<NL>, dim3(h->startup_qg.nblk + ld[0].nblk + ld[1].nblk + nzblk), dim3(kBlock), 0, s, lsS[0],
-                       lsP[0], lsS[1], lsP[1], crS, crP, mrS, mrP, lqS, lqP, ld[0], ld[1], z, nzblk, h->startup_qg);
-    h->startup_qg.nblk = 0;
+    hipLaunchKernelGGL(k_startup<NL>, dim3(req.startup_qg.nblk + ld[0].nblk + ld[1].nblk + nzblk), dim3(kBlock), 0, s, lsS[0],
+                       lsP[0], lsS[1], lsP[1], crS, crP, mrS, mrP, lqS, lqP, ld[0], ld[1], z, nzblk, req.startup_qg);
     h->launches++;
     bool ln_begun = false, minres_begun = false;
     if (any_lsqr) {
@@ -3199,15 +3241,13 @@ struct KrylovRun {
         seg[ns] = lsqr_upd_seg(l, it);
         seg[ns++].gate = lanes[NL - 1 - l].ctl;  // the other lane of the call (NL = 1: itself)
       }
-    if (h->absorb_flush && ns == 1) h->pending_flush = seg[0];  // applied by the tail's first kernel (k_ys)
+    TailCtx t;
+    t.gates = Gates{lanes[0].ctl, lanes[NL - 1].ctl};
+    if (req.absorb_flush && ns == 1) t.flush = seg[0];  // applied by the tail's first kernel (k_ys)
     else launch_updates<NL>(h, seg[0], seg[1], seg_none());
-    h->gate0 = lanes[0].ctl;
-    h->gate1 = lanes[NL - 1].ctl;
     const int64_t l0 = h->launches;
-    const int rc = (*tail)();
+    const int rc = (*tail)(t);
     tail_launches += h->launches - l0;  // (the caller's epilogue, not the loop: fpsq_info.last_loop_launches)
-    h->gate0 = h->gate1 = nullptr;
-    h->pending_flush.kind = UPD_NONE;
     if (rc) return rc;
     spec_it = it;
     return 0;
@@ -3311,7 +3351,7 @@ struct KrylovRun {
     if (spec_it >= 0 && spec_it == it && all_done()) {
       // every recurrence ended at or before the iteration the speculative flush + tail were enqueued behind: their gates
       // were open, the call's epilogue is already in the stream
-      h->tail_was_run = true;
+      res.tail_was_run = true;
       return 0;
     }
     // the last LSQR update (iteration `it`) has not been enqueued yet
@@ -3324,8 +3364,8 @@ struct KrylovRun {
       seg[1] = winit[1];
     }
     // MINRES: stage E3 and the stopping tests of the last enqueued iteration (no-ops when it ended earlier)
-    if (h->absorb_flush && tail != nullptr && ns == 1 && it >= 1 && minres_lane < 0)
-      h->pending_flush = seg[0];  // the caller's epilogue starts with k_ys, which applies it
+    if (req.absorb_flush && tail != nullptr && ns == 1 && it >= 1 && minres_lane < 0)
+      res.flush = seg[0];  // the caller's epilogue starts with k_ys, which applies it
     else
       launch_updates<NL>(h, seg[0], seg[1], minres_lane >= 0 && it >= 1 ? minres_seg(3, it, SPcur) : seg_none());
     if (minres_lane >= 0 && it >= 1)
@@ -3363,15 +3403,19 @@ struct KrylovRun {
 };
 
 template <int NL>
-int run_krylov(fpsq_handle h, Lane* lanes, const TailFn* tail = nullptr) {
-  return KrylovRun<NL>(h, lanes, tail).run();
+int run_krylov(fpsq_handle h, Lane* lanes, const TailFn* tail, const RunRequest& req, RunResult* res) {
+  KrylovRun<NL> r(h, lanes, tail, req);
+  const int rc = r.run();
+  if (res) *res = r.res;
+  return rc;
 }
 
-int run_lanes(fpsq_handle h, Lane* lanes, int nlanes, const TailFn* tail = nullptr) {
-  h->tail_was_run = false;
-  if (nlanes == 2 && h->opt.fuse_two_rhs) return run_krylov<2>(h, lanes, (!h->comm || h->halo) ? tail : nullptr);
+// (one recurrence after the other: the first run serves the request, and the caller runs its epilogue behind them)
+int run_lanes(fpsq_handle h, Lane* lanes, int nlanes, const TailFn* tail = nullptr, const RunRequest& req = {},
+              RunResult* res = nullptr) {
+  if (nlanes == 2 && h->opt.fuse_two_rhs) return run_krylov<2>(h, lanes, (!h->comm || h->halo) ? tail : nullptr, req, res);
   for (int l = 0; l < nlanes; ++l)
-    if (int rc = run_krylov<1>(h, lanes + l)) return rc;
+    if (int rc = run_krylov<1>(h, lanes + l, nullptr, l == 0 ? req : RunRequest{}, nullptr)) return rc;
   return 0;
 }
 
@@ -3474,9 +3518,6 @@ void order_inputs(fpsq_handle h) {
 }
 
 void call_begin(fpsq_handle h) {
-  h->absorb_flush = false;
-  h->pending_flush.kind = UPD_NONE;
-  h->startup_qg.nblk = 0;
   h->launches = 0;
   h->spmv_launches = 0;
   h->prod_a[0] = h->prod_a[1] = h->prod_at[0] = h->prod_at[1] = 0;
@@ -3675,9 +3716,6 @@ int minres_k_device(fpsq_handle h, const double* bp0, const double* bq0, const d
     return a;
   };
   launch_step_raw(h, sargs(STEP_MINRES_BEGIN, 0, 0), sargs(STEP_MINRES_BEGIN, 1, 0));
-  const LaneCtl* gsave0 = h->gate0;
-  const LaneCtl* gsave1 = h->gate1;
-  h->gate0 = h->gate1 = nullptr;
   int64_t it = 0, chunk = 8;
   int rc = 0;
   while (true) {
@@ -3706,8 +3744,6 @@ int minres_k_device(fpsq_handle h, const double* bp0, const double* bq0, const d
     if ((h->prog_host[0].done && h->prog_host[1].done) || it >= itmax) break;
     chunk = std::min<int64_t>(chunk * 2, 64);
   }
-  h->gate0 = gsave0;
-  h->gate1 = gsave1;
   if (rc) return rc;
   if (!(h->prog_host[0].done && h->prog_host[1].done)) {  // (the mapped words lag: read the states)
     MinresState hs[2];
@@ -3725,7 +3761,7 @@ int minres_k_device(fpsq_handle h, const double* bp0, const double* bq0, const d
 // affine_shift != null (fast start): c is NOT formed yet; CRAIG's right-hand side -(A z - shift), z in the long pair's
 // CRAIG lane, comes out of the LSQR start-up product and A z - shift is left in `c` (see run_krylov)
 int two_mixed_device(fpsq_handle h, const double* g, double* c, bool defer_p1 = false,
-                     const double* affine_shift = nullptr, const TailFn* tail = nullptr) {
+                     const double* affine_shift = nullptr, const TailFn* tail = nullptr, const RunRequest& req = {}) {
   if (h->opt.kkt_method == FPSQ_KKT_MINRES_K) {
     if (defer_p1 || affine_shift || tail) {
       h->err = "kkt_method = MINRES_K serves fpsq_solve_two_mixed / fpsq_solve_two_least_squares / fpsq_ys_gs only";
@@ -3756,14 +3792,15 @@ int two_mixed_device(fpsq_handle h, const double* g, double* c, bool defer_p1 = 
   lanes[1].y = h->Cy;
   lanes[1].st = &h->hstats[1];
   // p1 = rhs1 - Aop' q1                                                   :126-127
-  TailFn full = [&]() -> int {
+  TailFn full = [&](const TailCtx& t) -> int {
     if (!defer_p1)
-      if (int rc = at_product_const(h, -1.0, h->Lx[0], 1.0, g, h->p1)) return rc;
-    return tail ? (*tail)() : 0;
+      if (int rc = at_product_const(h, -1.0, h->Lx[0], 1.0, g, h->p1, t.gates)) return rc;
+    return tail ? (*tail)(t) : 0;
   };
-  if (int rc = run_lanes(h, lanes, 2, tail ? &full : nullptr)) return rc;
-  if (!h->tail_was_run)
-    if (int rc = full()) return rc;
+  RunResult r;
+  if (int rc = run_lanes(h, lanes, 2, tail ? &full : nullptr, req, &r)) return rc;
+  if (!r.tail_was_run)
+    if (int rc = full(TailCtx{Gates{}, r.flush})) return rc;
   return 0;
 }
 
@@ -3786,14 +3823,15 @@ int two_least_squares_device(fpsq_handle h, const double* r1, const double* r2, 
     lanes[l].st = &h->hstats[l];
   }
   // src/solve_linear_system.jl:90-91 and :99-100
-  TailFn full = [&]() -> int {
-    if (int rc = at_product_const(h, -1.0, h->Lx[0], 1.0, r1, h->p1)) return rc;
-    if (int rc = at_product_const(h, -1.0, h->Lx[1], 1.0, r2, h->p2b)) return rc;
-    return tail ? (*tail)() : 0;
+  TailFn full = [&](const TailCtx& t) -> int {
+    if (int rc = at_product_const(h, -1.0, h->Lx[0], 1.0, r1, h->p1, t.gates)) return rc;
+    if (int rc = at_product_const(h, -1.0, h->Lx[1], 1.0, r2, h->p2b, t.gates)) return rc;
+    return tail ? (*tail)(t) : 0;
   };
-  if (int rc = run_lanes(h, lanes, 2, tail ? &full : nullptr)) return rc;
-  if (!h->tail_was_run)
-    if (int rc = full()) return rc;
+  RunResult r;
+  if (int rc = run_lanes(h, lanes, 2, tail ? &full : nullptr, {}, &r)) return rc;
+  if (!r.tail_was_run)
+    if (int rc = full(TailCtx{Gates{}, r.flush})) return rc;
   return 0;
 }
 
@@ -4504,11 +4542,12 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
   // c = A x - b product and the right-hand-side loads of the start-up are not launched.
   const bool local_vec = !h->comm || h->halo;  // single GPU, or row-sharded with column windows (halo mode)
   const bool fast = local_vec && h->opt.fuse_two_rhs != 0 && h->opt.kkt_method == FPSQ_KKT_LSQR_CRAIG;
+  RunRequest req;
   {
     QpGradArgs qg{qp->q, qp->d, dx, dxk, h->g, n, h->pQ[0], h->pQ[1], fast ? h->LP : (double*)nullptr,
                   fast ? h->pE : (double*)nullptr, n_owned(h), gn};
     if (fast && !(h->ab_mask & 1)) {
-      h->startup_qg = qg;  // evaluated by the start-up launch of the recurrences (k_startup): no launch of its own
+      req.startup_qg = qg;  // evaluated by the start-up launch of the recurrences (k_startup): no launch of its own
     } else {
       hipLaunchKernelGGL(k_qp_grad, dim3(gn), dim3(kBlock), 0, s, qg);
       h->launches++;
@@ -4521,15 +4560,14 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
   // (halo mode: the same product, its overlap rows completed after the neighbour exchange; phi needs its all-reduce)
   const bool paired = local_vec && rho > 0.0;
   // the epilogue then starts with k_ys, which also applies the final LSQR x update (no launch of its own for it)
-  h->absorb_flush = paired && fast && !(h->ab_mask & 2);
+  req.absorb_flush = paired && fast && !(h->ab_mask & 2);
   const double seq = (h->call_seq += 1.0);
   // everything behind the two solves: enqueued speculatively (gated on the recurrences' `done` flags) by run_krylov when
   // the iteration count of the previous evaluation is known, else here
-  TailFn epi = [&]() -> int {
+  TailFn epi = [&](const TailCtx& t) -> int {
     // ys = q1 + sigma q2 and the dots of objgrad!
     hipLaunchKernelGGL(k_ys, dim3(gm), dim3(kBlock), 0, s, h->Lx[0], h->Cy, h->c, sigma, h->ys, m, h->pC[0], h->pC[1],
-                       paired ? h->SP : (double*)nullptr, h->gate0, h->gate1, h->pending_flush);
-    h->pending_flush.kind = UPD_NONE;
+                       paired ? h->SP : (double*)nullptr, t.gates.c0, t.gates.c1, t.flush);
     h->launches++;
     FxArgs fa{};
     fa.seq = seq;
@@ -4547,7 +4585,7 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
     const bool in_launch = insum(h);
     if (const XchTable* xt = in_launch ? insum_table(h) : nullptr) {
       fa.xt = xt;
-      fa.xseq = ++h->xch_seq;
+      fa.xseq = next_xseq(h);
     }
     FxArgs none = fa;
     none.out = nullptr;
@@ -4560,16 +4598,15 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
       // time -- 2 % of an evaluation.)
       const bool early_fx = in_launch && (h->ab_mask & 4);
       if (early_fx) {
-        hipLaunchKernelGGL(k_qp_fx, dim3(1), dim3(kBlock), 0, s, fa, h->gate0, h->gate1);
+        hipLaunchKernelGGL(k_qp_fx, dim3(1), dim3(kBlock), 0, s, fa, t.gates.c0, t.gates.c1);
         h->launches++;
       }
       const bool grad_fx = in_launch && !early_fx;
       // one GPU: the rows of the raw product go straight into grad(phi) -- one launch, and the 16 MB product is neither written nor
       // re-read (k_spmv<.., GRAD>; bitwise the two launches below, FPSQ_FUSE_TAIL=0)
       // (a communicator of ONE rank has no overlap rows and no peers: the single-GPU tail)
-      const bool alone = !h->comm || (h->comm->nranks == 1 && in_launch && h->ovl + h->ovr == 0);
-      const bool one_launch = h->fuse_tail && alone && h->AT.sorted && h->AT.padded;
-      if (one_launch) {
+      bool one_launch = false;
+      if (single_gpu_tail(h)) {
         GradEpi ge{};
         ge.g = h->g;
         ge.v = h->Cx;
@@ -4582,31 +4619,24 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
         ge.gs = h->gs;
         ge.gx = dgx;
         ge.fx = grad_fx ? fa : none;
-        h->tail_grad = &ge;
-        h->tail_grad_used = false;
-        launch_spmv<2>(h, TAG_AT, h->SP, nullptr, h->LP, h->ctl_raw, h->ctl_raw, nullptr, seg_none(), seg_none(), false);
-        h->tail_grad = nullptr;
-        if (!h->tail_grad_used) {  // (the product wrote its rows as ever: combine them in a launch of their own)
-          hipLaunchKernelGGL(k_qp_penalty_grad, dim3(grad_fx ? gn + 1 : gn), dim3(kBlock), 0, s, (const double*)nullptr, h->g, h->LP,
-                             h->Cx, qp->q, (const double*)nullptr, dx, dxk, sigma, rho, eta, h->gs, dgx, n, grad_fx ? fa : none,
-                             h->gate0, h->gate1);
-          h->launches++;
-        }
-      } else {
-        launch_spmv<2>(h, TAG_AT, h->SP, nullptr, h->LP, h->ctl_raw, h->ctl_raw, nullptr, seg_none(), seg_none(), h->halo);
+        one_launch = launch_at_tail<2>(h, h->SP, h->LP, ge, t.gates);
+      }
+      if (!one_launch) {  // (the product writes its rows as ever: combine them in a launch of their own)
+        launch_spmv<2>(h, TAG_AT, h->SP, nullptr, h->LP, h->ctl_raw, h->ctl_raw, nullptr, seg_none(), seg_none(), h->halo, nullptr,
+                       t.gates);
         if (h->halo)
-          if (int rc = halo_finish<2>(h, nullptr, h->LP, h->ctl_raw, h->ctl_raw, nullptr)) return rc;
+          if (int rc = halo_finish<2>(h, nullptr, h->LP, h->ctl_raw, h->ctl_raw, nullptr, t.gates)) return rc;
         hipLaunchKernelGGL(k_qp_penalty_grad, dim3(grad_fx ? gn + 1 : gn), dim3(kBlock), 0, s, (const double*)nullptr, h->g, h->LP,
                            h->Cx, qp->q, (const double*)nullptr, dx, dxk, sigma, rho, eta, h->gs, dgx, n, grad_fx ? fa : none,
-                           h->gate0, h->gate1);
+                           t.gates.c0, t.gates.c1);
         h->launches++;
       }
     } else {
       if (rho > 0.0)
-        if (int rc = at_product_const(h, 1.0, h->c, 0.0, nullptr, h->jc)) return rc;  // J'c   (:424-428)
+        if (int rc = at_product_const(h, 1.0, h->c, 0.0, nullptr, h->jc, t.gates)) return rc;  // J'c   (:424-428)
       hipLaunchKernelGGL(k_qp_penalty_grad, dim3(in_launch ? gn + 1 : gn), dim3(kBlock), 0, s, h->p1, h->g,
                          (const double*)nullptr, h->Cx, qp->q, h->jc, dx, dxk, sigma, rho, eta, h->gs, dgx, n,
-                         in_launch ? fa : none, h->gate0, h->gate1);
+                         in_launch ? fa : none, t.gates.c0, t.gates.c1);
       h->launches++;
     }
     if (!in_launch) {  // phi: c'ys and c'c are sums over the rank's rows only
@@ -4644,15 +4674,14 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
         fa.pcc = h->comm_scal + 1;
         fa.np_m = 1;
       }
-      hipLaunchKernelGGL(k_qp_fx, dim3(1), dim3(kBlock), 0, s, fa, h->gate0, h->gate1);
+      hipLaunchKernelGGL(k_qp_fx, dim3(1), dim3(kBlock), 0, s, fa, t.gates.c0, t.gates.c1);
       h->launches += 2;
     }
     return 0;
   };
-  if (int rc = two_mixed_device(h, h->g, h->c, paired, fast ? qp->b : nullptr, local_vec ? &epi : nullptr)) return rc;
+  if (int rc = two_mixed_device(h, h->g, h->c, paired, fast ? qp->b : nullptr, local_vec ? &epi : nullptr, req)) return rc;
   if (!local_vec)
-    if (int rc = epi()) return rc;
-  h->absorb_flush = false;
+    if (int rc = epi(TailCtx{})) return rc;
   if (gx && dgx != gx) HIPCHK(h, hipMemcpyAsync(gx, h->gx, nb, hipMemcpyDefault, s));
   if (ys) HIPCHK(h, hipMemcpyAsync(ys, h->ys, mb, hipMemcpyDefault, s));
   if (gs) HIPCHK(h, hipMemcpyAsync(gs, h->gs, nb, hipMemcpyDefault, s));
@@ -4700,14 +4729,13 @@ static int impl_qp_hprod(fpsq_handle h, fpsq_qp qp, const double* v, double sigm
   bool lsq_repeats = false;
   call_begin(h);
   hipLaunchKernelGGL(k_qp_hsv, dim3(gn), dim3(kBlock), 0, s, qp->q, dv, h->in_n2, n);                    // :537
-  TailFn epi = [&]() -> int {
+  TailFn epi = [&](const TailCtx& t) -> int {
     bool fin_done = false;
     if (rho > 0.0) {                                                                                      // :557-558
-      spmv_const(h, TAG_A, 1.0, dv, 0.0, nullptr, h->in_m);
+      spmv_const(h, TAG_A, 1.0, dv, 0.0, nullptr, h->in_m, t.gates);
       // one GPU: the rows of A'(A v) go straight into Hv (k_spmv<1, .., GRAD>; bitwise the product + k_qp_hprod_fin, FPSQ_FUSE_TAIL=0)
-      const bool alone = !h->comm || (h->comm->nranks == 1 && h->ovl + h->ovr == 0);
-      GradEpi ge{};
-      if (h->fuse_tail && alone && h->AT.sorted && h->AT.padded) {
+      if (single_gpu_tail(h)) {
+        GradEpi ge{};
         ge.p1 = h->p1;
         ge.p2 = h->p2b;
         ge.v = dv;
@@ -4716,17 +4744,14 @@ static int impl_qp_hprod(fpsq_handle h, fpsq_qp qp, const double* v, double sigm
         ge.rho = rho;
         ge.eta = eta;
         ge.hv = dhv;
-        h->tail_grad = &ge;
-        h->tail_grad_used = false;
+        fin_done = launch_at_tail<1>(h, h->in_m, h->jc, ge, t.gates);
       }
-      const int rc = at_product_const(h, 1.0, h->in_m, 0.0, nullptr, h->jc);
-      fin_done = h->tail_grad != nullptr && h->tail_grad_used;
-      h->tail_grad = nullptr;
-      if (rc) return rc;
+      if (!fin_done)
+        if (int rc = at_product_const(h, 1.0, h->in_m, 0.0, nullptr, h->jc, t.gates)) return rc;
     }
     if (!fin_done) {
       hipLaunchKernelGGL(k_qp_hprod_fin, dim3(gn), dim3(kBlock), 0, s, h->p1, h->p2b, qp->q, dv, h->jc, sigma, rho, eta, dhv,
-                         n, h->gate0, h->gate1);                                                          // :543-562
+                         n, t.gates.c0, t.gates.c1);                                                      // :543-562
       h->launches++;
     }
     h->launches++;
@@ -4735,7 +4760,7 @@ static int impl_qp_hprod(fpsq_handle h, fpsq_qp qp, const double* v, double sigm
   const bool local_vec = !h->comm || h->halo;
   if (int rc = two_least_squares_device(h, dv, h->in_n2, local_vec ? &epi : nullptr)) return rc;         // :542
   if (!local_vec)
-    if (int rc = epi()) return rc;
+    if (int rc = epi(TailCtx{})) return rc;
   if (hessian_approx == 1) {
     // Val(1) (src/model-Fletcherpenaltynlp.jl:572-634) adds, on top of everything above:
     //   Ssv = ghjvprod(x, gs, v) = 0 (linear constraints);  (invJtJJv, invJtJSsv) = solve_two_extras(v, Ssv)   :601-602

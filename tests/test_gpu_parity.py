@@ -1396,6 +1396,42 @@ def test_one_launch_tail_is_bitwise_the_two_launch_tail(monkeypatch, size, delta
     assert all(a < b for a, b in zip(l1[1:], l2[1:])) and l1[-1] + 1 == l2[-1], (l1, l2)
 
 
+def test_hprod_tail_on_a_replicated_communicator_of_one(monkeypatch):
+    """hprod! Val(2) on a row-sharded handle of ONE shard without halo (replicated n-vectors: --parallel shard-allreduce at world 1).
+    Its A'(A v) product needs no sum over the ranks, so the tail is the single-GPU one: k_spmv<1, .., GRAD> writes Hv as the row
+    epilogue of the product.  FPSQ_FUSE_TAIL=0 (raw product, all-reduce, k_axpby_plain into J'Jv, k_qp_hprod_fin) gives Hv bitwise,
+    with two kernel launches more; Hv matches a single-GPU handle's (the replicated loop forms its norms through other kernels)."""
+    from fps_amd.device_qp import LocalGroup
+    from fps_amd.distributed import shard_qp
+
+    qp = _small_pde(seed=23, n=24000, m=2400)
+    v = np.random.default_rng(5).standard_normal(qp.n)
+    ref = DeviceEqQP(qp, sigma=1e3, rho=1.0)
+    hv_ref = np.empty(qp.n)
+    assert ref.hprod(v, hv_ref, 2) == 0
+    ref.close()
+
+    def run():
+        group = LocalGroup(1)
+        dev = DeviceEqQP(shard_qp(qp, 0, qp.m), sigma=1e3, rho=1.0, comm=("local", group.ptr, 0))
+        hv = np.empty(qp.n)
+        rc = group.run([lambda: dev.hprod(v, hv, 2)])[0]
+        i = dev.info()
+        st = [(dev.stats[q].niter, dev.stats[q].status) for q in range(2)]
+        dev.close()
+        group.close()
+        assert rc == 0 and i["at_sorted"] != 0, i  # (the A' layout has a GRAD variant)
+        return hv, st, i["last_kernel_launches"]
+
+    monkeypatch.setenv("FPSQ_FUSE_TAIL", "0")
+    hv2, st2, l2 = run()
+    monkeypatch.setenv("FPSQ_FUSE_TAIL", "1")
+    hv1, st1, l1 = run()
+    assert np.array_equal(hv1, hv2) and st1 == st2
+    assert l2 - l1 == 2, (l1, l2)
+    assert _rel(hv1, hv_ref) < 1e-9
+
+
 @pytest.mark.parametrize("size", [(24000, 2400), (300000, 30000, "headline density")])
 def test_enqueueing_on_the_registered_stream_is_bitwise_the_own_stream(monkeypatch, size):
     """include/fpsq.h INPUT READINESS (round 5): with device-resident arguments whose producer stream is registered
