@@ -13,45 +13,36 @@
 
 using namespace fpsq;
 
-struct fpsq_dense_s {
-  int64_t n = 0, m = 0, npad = 0, mpad = 0, nb = 0;
+// What the dense and the banded direct handle share: everything around their numeric cores (storage and formation of M, the
+// elimination order).  Each handle derives from it and adds only its own storage.
+struct DirectCore {
+  const char* name = "";  // "dense" / "band": prefix of the state errors
+  int64_t n = 0, m = 0, mpad = 0, nb = 0;
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
-  bool have_jac = false, factored = false;
-  double* A = nullptr;     // mpad x npad, row-major, zero padded
-  double* M = nullptr;     // mpad x mpad: lower triangle holds the Cholesky factor after factorize
-  double* invs = nullptr;  // nb inverses of the diagonal 128 x 128 blocks of L
-  double* invsT = nullptr; // ... and their transposes (k_potrf_inv128m, k_trsv_step3)
-  int64_t regularized = 0; // pivots replaced by the dynamic regularisation in the last factorisation
-  double *r2 = nullptr, *y2 = nullptr, *x2 = nullptr, *part = nullptr;  // [mpad][2], [mpad][2], [npad][2], gemvt partials
+  bool factored = false;
+  double* invs = nullptr;   // nb inverses of the diagonal 128 x 128 blocks of L
+  double* invsT = nullptr;  // ... and their transposes (k_potrf_inv128m, k_trsv_step3)
+  double *r2 = nullptr, *y2 = nullptr;  // [mpad][2] each: right-hand sides / solutions of the two M-solves
   double *in_a = nullptr, *in_b = nullptr, *o_p1 = nullptr, *o_p2 = nullptr, *o_q1 = nullptr, *o_q2 = nullptr;
   int* info_dev = nullptr;
-  int nchunk = 16;
-  // (one generation of every kernel is left in the source: the sixteen-wave Gram product k_gemm_nt_f64_w16, the diagonal-block
-  // kernel k_potrf_inv128m, the single-round-trip step products k_gemm128_lds and the latency-organised solve step
-  // k_trsv_step3.  Their predecessors, the look-ahead and split-K variants -- all measured slower, DESIGN.md section 7 --
-  // and the environment switches that selected them were removed in round 3.)
-  double piv_tol = 0.0, piv_reg = 0.0;  // dynamic regularisation (fpsq_dense_set_regularization); reg <= 0: off
+  double piv_tol = 0.0, piv_reg = 0.0;  // dynamic regularisation (fpsq_*_set_regularization); reg <= 0: off
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   // the triangular sweeps in one launch each (k_trsv_chain): publication buffer, launch number, host-mapped error word
   unsigned long long* chain_pub = nullptr;
   unsigned long long* chain_err = nullptr;
   unsigned int chain_seq = 0;
-  bool chain = true;  // FPSQ_TRSV_CHAIN=0: one launch per step (k_trsv_step3)
+  bool chain = true;         // FPSQ_TRSV_CHAIN=0: one launch per step (k_trsv_step3)
   bool chain_break = false;  // FPSQ_DEBUG_CHAIN_BREAK=1 (tests): the workgroups publish a wrong launch number
-  // jac_coord! hand-over (fpsq_dense_set_structure_coo): the caller's COO entries sorted by target, duplicates grouped
-  int64_t coo_nnz = -1, coo_slots = 0;
+  // jac_coord! hand-over: the caller's COO entries sorted into slots (entries of A / of the CSR), duplicates grouped
+  int64_t coo_nnz = -1;
   int32_t *coo_perm = nullptr, *coo_slotptr = nullptr;
-  int64_t* coo_target = nullptr;
   double* coo_in = nullptr;
-  fpsq_dense_info info{};
   std::vector<void*> allocs;
 };
 
 namespace {
-thread_local std::string g_dense_create_error;
-
 // COO triplets (any order, duplicates allowed, `base`-based) -> row-major sorted slots.  order[k]: the caller's index of the
 // k-th sorted entry (stable: duplicates keep the caller's order); slotptr: one range of sorted entries per distinct (row,
 // col); srow / scol: the slots' coordinates.  Returns an error text, empty on success.
@@ -90,49 +81,195 @@ std::string coo_sort(int64_t m, int64_t n, int64_t nnz, const int64_t* rows, con
   return "";
 }
 
-#define DCHK(d, call)                                                          \
+#define CHK(c, call)                                                           \
   do {                                                                         \
     hipError_t e_ = (call);                                                    \
     if (e_ != hipSuccess) {                                                    \
-      (d)->err = std::string(#call) + ": " + hipGetErrorString(e_);            \
+      (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);            \
       return FPSQ_ERR_HIP;                                                     \
     }                                                                          \
   } while (0)
 
 template <class T>
-int dmalloc(fpsq_dense d, T** p, size_t count) {
+int dalloc(DirectCore* c, T** p, size_t count) {
   void* q = nullptr;
-  DCHK(d, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-  d->allocs.push_back(q);
+  CHK(c, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+  c->allocs.push_back(q);
   *p = (T*)q;
   return 0;
 }
 
-// q (m x 2 in d->r2, overwritten) <- M^-1 r2 via L y = r, L' q = y; result in d->y2 after the backward sweep
-void solve_two_rhs(fpsq_dense d) {
+// Set-up of the shared part on the handle's device (n, m, mpad, nb and the stream are the create function's: it owns the
+// error texts): events, the buffers every solve uses (`nlen`: the stored length of an n-vector), the chain publication
+// buffer, the host-mapped error word, the two environment switches.  Non-zero: failed, c->err says why.
+int core_setup(DirectCore* c, int64_t nlen) {
+  hipEventCreate(&c->e0);
+  hipEventCreate(&c->e1);
+  hipEventCreate(&c->e2);
+  const size_t inv_len = (size_t)c->nb * kDB * kDB;
+  int rc = dalloc(c, &c->invs, inv_len) | dalloc(c, &c->invsT, inv_len);
+  if (!rc) {  // k_potrf_inv128m writes the non-zero triangles only
+    hipMemset(c->invs, 0, inv_len * 8);
+    hipMemset(c->invsT, 0, inv_len * 8);
+  }
+  rc |= dalloc(c, &c->r2, (size_t)c->mpad * 2) | dalloc(c, &c->y2, (size_t)c->mpad * 2);
+  rc |= dalloc(c, &c->in_a, (size_t)nlen) | dalloc(c, &c->in_b, (size_t)std::max(nlen, c->mpad));
+  rc |= dalloc(c, &c->o_p1, (size_t)nlen) | dalloc(c, &c->o_p2, (size_t)nlen);
+  rc |= dalloc(c, &c->o_q1, (size_t)c->mpad) | dalloc(c, &c->o_q2, (size_t)c->mpad) | dalloc(c, &c->info_dev, 4);
+  const size_t pub_len = (size_t)c->nb * 512 + 8;  // (+ the abort word)
+  rc |= dalloc(c, &c->chain_pub, pub_len);
+  if (!rc) hipMemset(c->chain_pub, 0, pub_len * 8);
+  if (hipHostMalloc((void**)&c->chain_err, 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) rc = 1;
+  else *c->chain_err = 0;
+  if (const char* e = getenv("FPSQ_TRSV_CHAIN")) c->chain = atoi(e) != 0;
+  if (const char* e = getenv("FPSQ_DEBUG_CHAIN_BREAK")) c->chain_break = atoi(e) != 0;
+  return rc;
+}
+
+// ... and its tear-down, the stream included; the handle itself is the caller's to delete
+void core_teardown(DirectCore* c) {
+  hipSetDevice(c->device);
+  if (c->stream) hipStreamSynchronize(c->stream);
+  for (void* p : c->allocs) hipFree(p);
+  if (c->chain_err) hipHostFree(c->chain_err);
+  if (c->e0) hipEventDestroy(c->e0);
+  if (c->e1) hipEventDestroy(c->e1);
+  if (c->e2) hipEventDestroy(c->e2);
+  if (c->stream) hipStreamDestroy(c->stream);
+}
+
+int set_regularization(DirectCore* c, double tol, double reg) {
+  if (!c || !(tol >= 0.0)) return FPSQ_ERR_ARG;
+  c->piv_tol = tol;
+  c->piv_reg = reg;
+  return FPSQ_OK;
+}
+
+// jac_coord! hand-over: the caller's values (host or device) into `nslots` sorted slots of `out` (at target[slot] when given),
+// duplicates summed in the caller's order; left in flight on c->stream
+int coo_to_slots(DirectCore* c, const double* vals, const int64_t* target, double* out, int64_t nslots) {
+  CHK(c, hipMemcpyAsync(c->coo_in, vals, (size_t)c->coo_nnz * 8, hipMemcpyDefault, c->stream));
+  hipLaunchKernelGGL(k_coo_to_slots, dim3((unsigned)std::min<int64_t>((nslots + 255) / 256, 4096)), dim3(256), 0, c->stream,
+                     c->coo_in, c->coo_perm, c->coo_slotptr, target, out, nslots);
+  return FPSQ_OK;
+}
+
+// potrf + inverse of diagonal block k (at Mkk, leading dimension ld) on stream q; returns the inverse
+double* launch_potrf(DirectCore* c, hipStream_t q, double* Mkk, int ld, int k) {
+  double* inv = c->invs + (size_t)k * kDB * kDB;
+  hipLaunchKernelGGL(k_potrf_inv128m, dim3(1), dim3(kPotrfThreads5), kPotrfLds5, q, Mkk, ld, inv,
+                     c->invsT + (size_t)k * kDB * kDB, k * kDB, c->info_dev, c->piv_tol, c->piv_reg);
+  return inv;
+}
+
+// End of a factorisation whose caller recorded e0 (start) and e1 (M formed) on c->stream: device times, regularised pivots,
+// `factored`.  *pivot: first non-positive pivot row (1-based, stored numbering; 0: none).  Returns 1 (soft) when there is
+// one: M not positive definite (the reference warns and goes on, src/solve_linear_system.jl:242-246).
+int factor_end(DirectCore* c, double* form_ms, double* chol_ms, int64_t* regularized, int32_t* pivot) {
+  hipEventRecord(c->e2, c->stream);
+  int32_t hinfo[2] = {0, 0};
+  CHK(c, hipMemcpyAsync(hinfo, c->info_dev, 8, hipMemcpyDeviceToHost, c->stream));
+  CHK(c, hipStreamSynchronize(c->stream));
+  float a = 0.f, b = 0.f;
+  hipEventElapsedTime(&a, c->e0, c->e1);
+  hipEventElapsedTime(&b, c->e1, c->e2);
+  *form_ms = a;
+  *chol_ms = b;
+  *regularized = hinfo[1];
+  *pivot = hinfo[0];
+  c->factored = hinfo[0] == 0;
+  return hinfo[0] == 0 ? FPSQ_OK : 1;
+}
+
+// The two triangular sweeps in one launch each: c->r2 <- M^-1 c->r2 via L y = r (into c->y2), L' q = y, with the factor at
+// M (leading dimension ld).  band_w / chain_safe / chain_bw: the band geometry, 0 / 0 / 0 for a full lower triangle.
+// (tickets: word 1 behind the publication buffer counts every workgroup of every sweep of this handle, nb per launch)
+void chain_sweeps(DirectCore* c, const double* M, int ld, int band_w, int chain_safe, int chain_bw) {
+  const int nb = (int)c->nb;
+  ChainArgs a{c->chain_pub, 0, 0, nb, band_w, chain_safe, chain_bw, c->chain_err, c->chain_pub + (size_t)nb * 512 + 1, 0};
+  auto next = [&] {
+    a.seq = ++c->chain_seq;
+    a.pubseq = c->chain_break ? ~a.seq : a.seq;
+    a.ticket_base = (unsigned long long)(c->chain_seq - 1) * nb;
+  };
+  next();
+  hipLaunchKernelGGL(k_trsv_chain<true>, dim3(nb), dim3(256), 0, c->stream, M, ld, c->invs, c->invsT, c->r2, c->y2, a);
+  next();
+  hipLaunchKernelGGL(k_trsv_chain<false>, dim3(nb), dim3(256), 0, c->stream, M, ld, c->invs, c->invsT, c->y2, c->r2, a);
+}
+
+// Start of a solve_two_* call: argument and state checks, the two right-hand sides staged in in_a / in_b (rhs1: n doubles,
+// rhs2: m when `mixed`, else n), e0
+int solve_begin(DirectCore* c, bool mixed, const double* rhs1, const double* rhs2, const double* p1, const double* q1,
+                const double* p2, const double* q2) {
+  if (!c || !rhs1 || !rhs2 || !p1 || !q1 || !p2 || !q2) return FPSQ_ERR_ARG;
+  if (!c->factored) {
+    c->err = std::string(c->name) + "_solve: no valid factorisation";
+    return FPSQ_ERR_STATE;
+  }
+  hipSetDevice(c->device);
+  CHK(c, hipMemcpyAsync(c->in_a, rhs1, (size_t)c->n * 8, hipMemcpyDefault, c->stream));
+  CHK(c, hipMemcpyAsync(c->in_b, rhs2, (size_t)(mixed ? c->m : c->n) * 8, hipMemcpyDefault, c->stream));
+  hipEventRecord(c->e0, c->stream);
+  return FPSQ_OK;
+}
+
+// ... and its end, the results being in flight in o_p1 .. o_q2: e1, the copies to the caller, the check of the sweeps' error word
+int solve_end(DirectCore* c, double* p1, double* q1, double* p2, double* q2, double* solve_ms) {
+  hipStream_t s = c->stream;
+  hipEventRecord(c->e1, s);
+  CHK(c, hipMemcpyAsync(p1, c->o_p1, (size_t)c->n * 8, hipMemcpyDefault, s));
+  CHK(c, hipMemcpyAsync(p2, c->o_p2, (size_t)c->n * 8, hipMemcpyDefault, s));
+  CHK(c, hipMemcpyAsync(q1, c->o_q1, (size_t)c->m * 8, hipMemcpyDefault, s));
+  CHK(c, hipMemcpyAsync(q2, c->o_q2, (size_t)c->m * 8, hipMemcpyDefault, s));
+  CHK(c, hipStreamSynchronize(s));
+  if (c->chain_err && *c->chain_err) {
+    *c->chain_err = 0;
+    c->err = "triangular sweep: a block's solution did not arrive (bounded wait expired); FPSQ_TRSV_CHAIN=0 avoids the path";
+    return FPSQ_ERR_TIMEOUT;
+  }
+  float ms = 0.f;
+  hipEventElapsedTime(&ms, c->e0, c->e1);
+  *solve_ms = ms;
+  return FPSQ_OK;
+}
+}  // namespace
+
+// ===================================================================================================== dense M
+
+struct fpsq_dense_s : DirectCore {
+  int64_t npad = 0;
+  bool have_jac = false;
+  double* A = nullptr;  // mpad x npad, row-major, zero padded
+  double* M = nullptr;  // mpad x mpad: lower triangle holds the Cholesky factor after factorize
+  double *x2 = nullptr, *part = nullptr;  // [npad][2], gemvt partials
+  int nchunk = 16;
+  // (one generation of every kernel is left in the source: the sixteen-wave Gram product k_gemm_nt_f64_w16, the diagonal-block
+  // kernel k_potrf_inv128m, the single-round-trip step products k_gemm128_lds and the latency-organised solve step
+  // k_trsv_step3.  Their predecessors, the look-ahead and split-K variants -- all measured slower, DESIGN.md section 7 --
+  // and the environment switches that selected them were removed in round 3.)
+  // fpsq_dense_set_structure_coo: where each sorted slot lies in A
+  int64_t coo_slots = 0;
+  int64_t* coo_target = nullptr;
+  fpsq_dense_info info{};
+};
+
+namespace {
+thread_local std::string g_dense_create_error;
+
+// q (m x 2 in d->r2, overwritten) <- M^-1 r2 via L y = r, L' q = y; the solution ends up in d->r2
+void dense_sweeps(fpsq_dense d) {
+  if (d->chain) return chain_sweeps(d, d->M, (int)d->mpad, 0, 0, 0);
   hipStream_t s = d->stream;
   const int nb = (int)d->nb, ld = (int)d->mpad;
-  if (d->chain) {
-    // (tickets: word 1 behind the publication buffer counts every workgroup of every sweep of this handle, nb per launch)
-    ChainArgs c{d->chain_pub, ++d->chain_seq, 0, nb, 0, 0, 0, d->chain_err, d->chain_pub + (size_t)nb * 512 + 1, 0};
-    c.pubseq = d->chain_break ? ~c.seq : c.seq;
-    c.ticket_base = (unsigned long long)(d->chain_seq - 1) * nb;
-    hipLaunchKernelGGL(k_trsv_chain<true>, dim3(nb), dim3(256), 0, s, d->M, ld, d->invs, d->invsT, d->r2, d->y2, c);
-    c.seq = ++d->chain_seq;
-    c.pubseq = d->chain_break ? ~c.seq : c.seq;
-    c.ticket_base = (unsigned long long)(d->chain_seq - 1) * nb;
-    hipLaunchKernelGGL(k_trsv_chain<false>, dim3(nb), dim3(256), 0, s, d->M, ld, d->invs, d->invsT, d->y2, d->r2, c);
-    return;
-  }
   for (int k = 0; k < nb; ++k)
     hipLaunchKernelGGL(k_trsv_step3<true>, dim3(nb - k), dim3(256), 0, s, d->M, ld, d->invs, d->invsT, d->r2, d->y2, k, 0);
   for (int k = nb - 1; k >= 0; --k)
     hipLaunchKernelGGL(k_trsv_step3<false>, dim3(k + 1), dim3(256), 0, s, d->M, ld, d->invs, d->invsT, d->y2, d->r2, k, 0);
-  // solution now in d->r2
 }
 
 // common tail: Q in d->r2 ([mpad][2]); P = [a0, a1] - A' Q
-int finish(fpsq_dense d, const double* a0, const double* a1, double* p1, double* q1, double* p2, double* q2) {
+int dense_finish(fpsq_dense d, const double* a0, const double* a1, double* p1, double* q1, double* p2, double* q2) {
   hipStream_t s = d->stream;
   const int rows_per_chunk = (int)((d->mpad + d->nchunk - 1) / d->nchunk);
   hipLaunchKernelGGL(k_dense_gemvt_part<2>, dim3((unsigned)((d->npad + 255) / 256), d->nchunk), dim3(256), 0, s, d->A,
@@ -141,21 +278,7 @@ int finish(fpsq_dense d, const double* a0, const double* a1, double* p1, double*
                      (int)d->npad, (int)d->n, a0, a1, d->o_p1, d->o_p2);
   hipLaunchKernelGGL(k_dense_unpack2, dim3((unsigned)((d->m + 255) / 256)), dim3(256), 0, s, d->r2, d->o_q1, d->o_q2,
                      (int)d->m);
-  hipEventRecord(d->e1, s);
-  DCHK(d, hipMemcpyAsync(p1, d->o_p1, (size_t)d->n * 8, hipMemcpyDefault, s));
-  DCHK(d, hipMemcpyAsync(p2, d->o_p2, (size_t)d->n * 8, hipMemcpyDefault, s));
-  DCHK(d, hipMemcpyAsync(q1, d->o_q1, (size_t)d->m * 8, hipMemcpyDefault, s));
-  DCHK(d, hipMemcpyAsync(q2, d->o_q2, (size_t)d->m * 8, hipMemcpyDefault, s));
-  DCHK(d, hipStreamSynchronize(s));
-  if (d->chain_err && *d->chain_err) {
-    *d->chain_err = 0;
-    d->err = "triangular sweep: a block's solution did not arrive (bounded wait expired); FPSQ_TRSV_CHAIN=0 avoids the path";
-    return FPSQ_ERR_TIMEOUT;
-  }
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, d->e0, d->e1);
-  d->info.last_solve_ms = ms;
-  return FPSQ_OK;
+  return solve_end(d, p1, q1, p2, q2, &d->info.last_solve_ms);
 }
 }  // namespace
 
@@ -179,6 +302,7 @@ int fpsq_dense_create(fpsq_dense* out, int64_t n, int64_t m, int32_t device) {
   d->n = n;
   d->m = m;
   d->device = device;
+  d->name = "dense";
   d->mpad = (m + kDB - 1) / kDB * kDB;
   d->npad = (n + kW16Kd - 1) / kW16Kd * kW16Kd;  // whole k-stages of the Gram product
   d->nb = d->mpad / kDB;
@@ -188,35 +312,11 @@ int fpsq_dense_create(fpsq_dense* out, int64_t n, int64_t m, int32_t device) {
     delete d;
     return FPSQ_ERR_HIP;
   }
-  hipEventCreate(&d->e0);
-  hipEventCreate(&d->e1);
-  hipEventCreate(&d->e2);
-  int rc = 0;
-  rc |= dmalloc(d, &d->A, (size_t)d->mpad * d->npad);
-  rc |= dmalloc(d, &d->M, (size_t)d->mpad * d->mpad);
-  rc |= dmalloc(d, &d->invs, (size_t)d->nb * kDB * kDB);
-  rc |= dmalloc(d, &d->invsT, (size_t)d->nb * kDB * kDB);
-  if (!rc) {  // k_potrf_inv128m writes the non-zero triangles only
-    hipMemset(d->invs, 0, (size_t)d->nb * kDB * kDB * 8);
-    hipMemset(d->invsT, 0, (size_t)d->nb * kDB * kDB * 8);
-  }
-  rc |= dmalloc(d, &d->r2, (size_t)d->mpad * 2);
-  rc |= dmalloc(d, &d->y2, (size_t)d->mpad * 2);
-  rc |= dmalloc(d, &d->x2, (size_t)d->npad * 2);
-  rc |= dmalloc(d, &d->part, (size_t)d->nchunk * d->npad * 2);
-  rc |= dmalloc(d, &d->in_a, (size_t)d->npad);
-  rc |= dmalloc(d, &d->in_b, (size_t)std::max(d->npad, d->mpad));
-  rc |= dmalloc(d, &d->o_p1, (size_t)d->npad);
-  rc |= dmalloc(d, &d->o_p2, (size_t)d->npad);
-  rc |= dmalloc(d, &d->o_q1, (size_t)d->mpad);
-  rc |= dmalloc(d, &d->o_q2, (size_t)d->mpad);
-  rc |= dmalloc(d, &d->info_dev, 4);
-  rc |= dmalloc(d, &d->chain_pub, (size_t)d->nb * 512 + 8);  // (+ the abort word)
-  if (!rc) hipMemset(d->chain_pub, 0, ((size_t)d->nb * 512 + 8) * 8);
-  if (hipHostMalloc((void**)&d->chain_err, 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) rc = 1;
-  else *d->chain_err = 0;
-  if (const char* e = getenv("FPSQ_TRSV_CHAIN")) d->chain = atoi(e) != 0;
-  if (const char* e = getenv("FPSQ_DEBUG_CHAIN_BREAK")) d->chain_break = atoi(e) != 0;
+  int rc = core_setup(d, d->npad);
+  rc |= dalloc(d, &d->A, (size_t)d->mpad * d->npad);
+  rc |= dalloc(d, &d->M, (size_t)d->mpad * d->mpad);
+  rc |= dalloc(d, &d->x2, (size_t)d->npad * 2);
+  rc |= dalloc(d, &d->part, (size_t)d->nchunk * d->npad * 2);
   if (rc) {
     g_dense_create_error = d->err;
     fpsq_dense_destroy(d);
@@ -237,14 +337,7 @@ int fpsq_dense_create(fpsq_dense* out, int64_t n, int64_t m, int32_t device) {
 
 int fpsq_dense_destroy(fpsq_dense d) {
   if (!d) return FPSQ_ERR_ARG;
-  hipSetDevice(d->device);
-  if (d->stream) hipStreamSynchronize(d->stream);
-  for (void* p : d->allocs) hipFree(p);
-  if (d->chain_err) hipHostFree(d->chain_err);
-  if (d->e0) hipEventDestroy(d->e0);
-  if (d->e1) hipEventDestroy(d->e1);
-  if (d->e2) hipEventDestroy(d->e2);
-  if (d->stream) hipStreamDestroy(d->stream);
+  core_teardown(d);
   delete d;
   return FPSQ_OK;
 }
@@ -252,9 +345,9 @@ int fpsq_dense_destroy(fpsq_dense d) {
 int fpsq_dense_set_jacobian(fpsq_dense d, const double* a_rowmajor) {
   if (!d || !a_rowmajor) return FPSQ_ERR_ARG;
   hipSetDevice(d->device);
-  DCHK(d, hipMemcpy2DAsync(d->A, (size_t)d->npad * 8, a_rowmajor, (size_t)d->n * 8, (size_t)d->n * 8, (size_t)d->m,
-                           hipMemcpyDefault, d->stream));
-  DCHK(d, hipStreamSynchronize(d->stream));
+  CHK(d, hipMemcpy2DAsync(d->A, (size_t)d->npad * 8, a_rowmajor, (size_t)d->n * 8, (size_t)d->n * 8, (size_t)d->m,
+                          hipMemcpyDefault, d->stream));
+  CHK(d, hipStreamSynchronize(d->stream));
   d->have_jac = true;
   d->factored = false;
   return FPSQ_OK;
@@ -265,8 +358,8 @@ int fpsq_dense_set_structure_coo(fpsq_dense d, int64_t nnz, const int64_t* rows,
   hipSetDevice(d->device);
   std::vector<int64_t> r(nnz), c(nnz);
   if (nnz) {
-    DCHK(d, hipMemcpy(r.data(), rows, (size_t)nnz * 8, hipMemcpyDefault));
-    DCHK(d, hipMemcpy(c.data(), cols, (size_t)nnz * 8, hipMemcpyDefault));
+    CHK(d, hipMemcpy(r.data(), rows, (size_t)nnz * 8, hipMemcpyDefault));
+    CHK(d, hipMemcpy(c.data(), cols, (size_t)nnz * 8, hipMemcpyDefault));
   }
   std::vector<int32_t> order, slotptr, srow, scol;
   const std::string msg = coo_sort(d->m, d->n, nnz, r.data(), c.data(), index_base, order, slotptr, srow, scol);
@@ -288,15 +381,15 @@ int fpsq_dense_set_structure_coo(fpsq_dense d, int64_t nnz, const int64_t* rows,
     *q = nullptr;
   }
   d->coo_nnz = -1;
-  if (dmalloc(d, &d->coo_perm, (size_t)std::max<int64_t>(nnz, 1)) || dmalloc(d, &d->coo_in, (size_t)std::max<int64_t>(nnz, 1)) ||
-      dmalloc(d, &d->coo_target, target.size()) || (dup && dmalloc(d, &d->coo_slotptr, slotptr.size())))
+  if (dalloc(d, &d->coo_perm, (size_t)std::max<int64_t>(nnz, 1)) || dalloc(d, &d->coo_in, (size_t)std::max<int64_t>(nnz, 1)) ||
+      dalloc(d, &d->coo_target, target.size()) || (dup && dalloc(d, &d->coo_slotptr, slotptr.size())))
     return FPSQ_ERR_HIP;
-  if (nnz) DCHK(d, hipMemcpy(d->coo_perm, order.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
-  DCHK(d, hipMemcpy(d->coo_target, target.data(), target.size() * 8, hipMemcpyHostToDevice));
-  if (dup) DCHK(d, hipMemcpy(d->coo_slotptr, slotptr.data(), slotptr.size() * 4, hipMemcpyHostToDevice));
+  if (nnz) CHK(d, hipMemcpy(d->coo_perm, order.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
+  CHK(d, hipMemcpy(d->coo_target, target.data(), target.size() * 8, hipMemcpyHostToDevice));
+  if (dup) CHK(d, hipMemcpy(d->coo_slotptr, slotptr.data(), slotptr.size() * 4, hipMemcpyHostToDevice));
   // entries outside the pattern are zero for good: the value hand-over only rewrites the pattern's slots
-  DCHK(d, hipMemsetAsync(d->A, 0, (size_t)d->mpad * d->npad * 8, d->stream));
-  DCHK(d, hipStreamSynchronize(d->stream));
+  CHK(d, hipMemsetAsync(d->A, 0, (size_t)d->mpad * d->npad * 8, d->stream));
+  CHK(d, hipStreamSynchronize(d->stream));
   d->coo_nnz = nnz;
   d->coo_slots = ns;
   d->have_jac = false;
@@ -309,12 +402,9 @@ int fpsq_dense_set_jacobian_coo(fpsq_dense d, const double* vals) {
     return FPSQ_ERR_ARG;
   }
   hipSetDevice(d->device);
-  if (d->coo_nnz > 0) {
-    DCHK(d, hipMemcpyAsync(d->coo_in, vals, (size_t)d->coo_nnz * 8, hipMemcpyDefault, d->stream));
-    hipLaunchKernelGGL(k_coo_to_slots, dim3((unsigned)std::min<int64_t>((d->coo_slots + 255) / 256, 4096)), dim3(256), 0,
-                       d->stream, d->coo_in, d->coo_perm, d->coo_slotptr, d->coo_target, d->A, d->coo_slots);
-  }
-  DCHK(d, hipStreamSynchronize(d->stream));
+  if (d->coo_nnz > 0)
+    if (int rc = coo_to_slots(d, vals, d->coo_target, d->A, d->coo_slots)) return rc;
+  CHK(d, hipStreamSynchronize(d->stream));
   d->have_jac = true;
   d->factored = false;
   return FPSQ_OK;
@@ -329,7 +419,7 @@ int fpsq_dense_factorize(fpsq_dense d, double delta, int32_t* info) {
   hipSetDevice(d->device);
   hipStream_t s = d->stream;
   const int nb = (int)d->nb, ld = (int)d->mpad;
-  DCHK(d, hipMemsetAsync(d->info_dev, 0, 8, s));
+  CHK(d, hipMemsetAsync(d->info_dev, 0, 8, s));
   hipEventRecord(d->e0, s);
   // M = A A' (lower tiles) on the fp64 matrix cores, then + delta I
   hipLaunchKernelGGL(k_gemm_nt_f64_w16<true>, dim3(nb, nb), dim3(1024), kW16Lds, s, d->M, ld, d->A, (int)d->npad, d->A,
@@ -341,9 +431,7 @@ int fpsq_dense_factorize(fpsq_dense d, double delta, int32_t* info) {
   // L_ik = M_ik Linv_kk' and trailing update M_ij -= L_ik L_jk' on the matrix cores
   for (int k = 0; k < nb; ++k) {
     double* Mkk = d->M + (size_t)k * kDB * ld + (size_t)k * kDB;
-    double* inv = d->invs + (size_t)k * kDB * kDB;
-    hipLaunchKernelGGL(k_potrf_inv128m, dim3(1), dim3(kPotrfThreads5), kPotrfLds5, s, Mkk, ld, inv,
-                       d->invsT + (size_t)k * kDB * kDB, k * kDB, d->info_dev, d->piv_tol, d->piv_reg);
+    double* inv = launch_potrf(d, s, Mkk, ld, k);
     const int rem = nb - k - 1;
     if (rem > 0) {  // the K = 128 products of the step, each in one memory round trip (k_gemm128_lds)
       double* panel = d->M + (size_t)(k + 1) * kDB * ld + (size_t)k * kDB;
@@ -354,42 +442,18 @@ int fpsq_dense_factorize(fpsq_dense d, double delta, int32_t* info) {
                          BlockStrides{});
     }
   }
-  hipEventRecord(d->e2, s);
-  int32_t hinfo2[2] = {0, 0};
-  DCHK(d, hipMemcpyAsync(hinfo2, d->info_dev, 8, hipMemcpyDeviceToHost, s));
-  DCHK(d, hipStreamSynchronize(s));
-  float a = 0.f, b = 0.f;
-  hipEventElapsedTime(&a, d->e0, d->e1);
-  hipEventElapsedTime(&b, d->e1, d->e2);
-  d->info.last_syrk_ms = a;
-  d->info.last_chol_ms = b;
-  const int32_t hinfo = hinfo2[0];
-  d->regularized = hinfo2[1];
-  d->info.regularized_pivots = hinfo2[1];
-  if (info) *info = hinfo;
-  d->factored = hinfo == 0;
-  return hinfo == 0 ? FPSQ_OK : 1;  // soft failure: M not positive definite (the reference warns and goes on, :244-246)
+  int32_t pivot = 0;
+  const int rc = factor_end(d, &d->info.last_syrk_ms, &d->info.last_chol_ms, &d->info.regularized_pivots, &pivot);
+  if (rc >= 0 && info) *info = pivot;
+  return rc;
 }
 
-int fpsq_dense_set_regularization(fpsq_dense d, double tol, double reg) {
-  if (!d || !(tol >= 0.0)) return FPSQ_ERR_ARG;
-  d->piv_tol = tol;
-  d->piv_reg = reg;
-  return FPSQ_OK;
-}
+int fpsq_dense_set_regularization(fpsq_dense d, double tol, double reg) { return set_regularization(d, tol, reg); }
 
 int fpsq_dense_solve_two_mixed(fpsq_dense d, const double* rhs1, const double* rhs2, double* p1, double* q1, double* p2,
                                double* q2) {
-  if (!d || !rhs1 || !rhs2 || !p1 || !q1 || !p2 || !q2) return FPSQ_ERR_ARG;
-  if (!d->factored) {
-    d->err = "dense_solve: no valid factorisation";
-    return FPSQ_ERR_STATE;
-  }
-  hipSetDevice(d->device);
+  if (int rc = solve_begin(d, true, rhs1, rhs2, p1, q1, p2, q2)) return rc;
   hipStream_t s = d->stream;
-  DCHK(d, hipMemcpyAsync(d->in_a, rhs1, (size_t)d->n * 8, hipMemcpyDefault, s));
-  DCHK(d, hipMemcpyAsync(d->in_b, rhs2, (size_t)d->m * 8, hipMemcpyDefault, s));
-  hipEventRecord(d->e0, s);
   // r = [A g, -c]:  q1 = M^-1 A g,  q2 = -M^-1 c   
   hipLaunchKernelGGL(k_dense_pack2, dim3((unsigned)((d->npad + 255) / 256)), dim3(256), 0, s, d->in_a, 1.0,
                      (const double*)nullptr, 0.0, d->x2, (int)d->n, (int)d->npad);
@@ -399,43 +463,40 @@ int fpsq_dense_solve_two_mixed(fpsq_dense d, const double* rhs1, const double* r
                      (int)d->mpad);
   hipLaunchKernelGGL(k_dense_pack2, dim3((unsigned)((d->mpad + 255) / 256)), dim3(256), 0, s, d->o_q1, 1.0, d->in_b, -1.0,
                      d->r2, (int)d->m, (int)d->mpad);
-  solve_two_rhs(d);
-  return finish(d, d->in_a, nullptr, p1, q1, p2, q2);
+  dense_sweeps(d);
+  return dense_finish(d, d->in_a, nullptr, p1, q1, p2, q2);
 }
 
 int fpsq_dense_solve_two_least_squares(fpsq_dense d, const double* rhs1, const double* rhs2, double* p1, double* q1,
                                        double* p2, double* q2) {
-  if (!d || !rhs1 || !rhs2 || !p1 || !q1 || !p2 || !q2) return FPSQ_ERR_ARG;
-  if (!d->factored) {
-    d->err = "dense_solve: no valid factorisation";
-    return FPSQ_ERR_STATE;
-  }
-  hipSetDevice(d->device);
+  if (int rc = solve_begin(d, false, rhs1, rhs2, p1, q1, p2, q2)) return rc;
   hipStream_t s = d->stream;
-  DCHK(d, hipMemcpyAsync(d->in_a, rhs1, (size_t)d->n * 8, hipMemcpyDefault, s));
-  DCHK(d, hipMemcpyAsync(d->in_b, rhs2, (size_t)d->n * 8, hipMemcpyDefault, s));
-  hipEventRecord(d->e0, s);
   hipLaunchKernelGGL(k_dense_pack2, dim3((unsigned)((d->npad + 255) / 256)), dim3(256), 0, s, d->in_a, 1.0, d->in_b, 1.0,
                      d->x2, (int)d->n, (int)d->npad);
   hipLaunchKernelGGL(k_dense_gemv<2>, dim3((unsigned)((d->mpad + 3) / 4)), dim3(256), 0, s, d->A, (int)d->npad,
                      (int)d->mpad, (int)d->npad, d->x2, 1.0, (const double*)nullptr, 0.0, d->r2);
-  solve_two_rhs(d);
-  return finish(d, d->in_a, d->in_b, p1, q1, p2, q2);
+  dense_sweeps(d);
+  return dense_finish(d, d->in_a, d->in_b, p1, q1, p2, q2);
 }
 
 int fpsq_dense_get_factor(fpsq_dense d, double* l_out) {
   if (!d || !l_out) return FPSQ_ERR_ARG;
   hipSetDevice(d->device);
-  DCHK(d, hipMemcpy2D(l_out, (size_t)d->m * 8, d->M, (size_t)d->mpad * 8, (size_t)d->m * 8, (size_t)d->m, hipMemcpyDefault));
+  CHK(d, hipMemcpy2D(l_out, (size_t)d->m * 8, d->M, (size_t)d->mpad * 8, (size_t)d->m * 8, (size_t)d->m, hipMemcpyDefault));
   return FPSQ_OK;
 }
 
-// ===================================================================================== sparse direct path (block band)
-
+int fpsq_dense_get_info(fpsq_dense d, fpsq_dense_info* info) {
+  if (!d || !info) return FPSQ_ERR_ARG;
+  *info = d->info;
+  return FPSQ_OK;
+}
 }  // extern "C"
 
-struct fpsq_band_s {
-  int64_t n = 0, m = 0, nnz = 0, mpad = 0, nb = 0;
+// ===================================================================================== sparse direct path (block band)
+
+struct fpsq_band_s : DirectCore {
+  int64_t nnz = 0;
   int band_w = 1;  // blocks per block row of the band storage = half bandwidth (in blocks) + 1
   int span = 0;    // widest column span of a row (LDS window of k_band_form)
   // row reordering chosen by the symbolic phase (reverse Cuthill-McKee on the rows of A, adjacent = sharing a column):
@@ -448,54 +509,19 @@ struct fpsq_band_s {
   int32_t *rperm = nullptr, *vperm = nullptr;
   double *vals_in = nullptr, *in_bp = nullptr;
   int form_gen = 2, form_R = 1;  // 2: k_band_form_t (by columns of A, form_R rows per pass); 1: k_band_form (row pairs)
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  bool factored = false;
   int32_t *rowptr = nullptr, *colind = nullptr, *t_rowptr = nullptr, *t_colind = nullptr, *t_perm = nullptr;
   int2* rowspan = nullptr;
   double *vals = nullptr, *t_vals = nullptr;
   double* Mb = nullptr;    // nb x band_w blocks of 128 x 128
-  double *invs = nullptr, *invsT = nullptr;
-  double *xn = nullptr, *ym = nullptr, *r2 = nullptr, *y2 = nullptr, *atq = nullptr;  // [n][2], [mpad][2] x 3, [n][2]
-  double *in_a = nullptr, *in_b = nullptr, *o_p1 = nullptr, *o_p2 = nullptr, *o_q1 = nullptr, *o_q2 = nullptr;
-  int* info_dev = nullptr;
-  double piv_tol = 0.0, piv_reg = 0.0;
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+  double *xn = nullptr, *ym = nullptr, *atq = nullptr;  // [n][2], [mpad][2], [n][2]
   hipStream_t stream2 = nullptr;  // the second elimination chain
-  unsigned long long* chain_pub = nullptr;  // k_trsv_chain, as in fpsq_dense_s
-  unsigned long long* chain_err = nullptr;
-  unsigned int chain_seq = 0;
-  bool chain = true, chain_break = false;
   hipEvent_t evA = nullptr, evB = nullptr;
-  // jac_coord! hand-over (fpsq_band_create_coo): the caller's COO entries sorted into the CSR slots
-  int64_t coo_nnz = -1;
-  int32_t *coo_perm = nullptr, *coo_slotptr = nullptr;
-  double *coo_in = nullptr, *csr_in = nullptr;
+  double* csr_in = nullptr;  // fpsq_band_create_coo: the CSR slots the sorted COO entries are summed into
   fpsq_band_info info{};
-  std::vector<void*> allocs;
 };
 
 namespace {
 thread_local std::string g_band_create_error;
-
-#define BCHK(b, call)                                                          \
-  do {                                                                         \
-    hipError_t e_ = (call);                                                    \
-    if (e_ != hipSuccess) {                                                    \
-      (b)->err = std::string(#call) + ": " + hipGetErrorString(e_);            \
-      return FPSQ_ERR_HIP;                                                     \
-    }                                                                          \
-  } while (0)
-
-template <class T>
-int bmalloc(fpsq_band b, T** p, size_t count) {
-  void* q = nullptr;
-  BCHK(b, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-  b->allocs.push_back(q);
-  *p = (T*)q;
-  return 0;
-}
 
 // Reverse Cuthill-McKee on the rows of A (two rows adjacent when they share a column: the graph of A A').  Returns the new
 // order (position -> caller's row) or an empty vector when the adjacency is too large to walk (sum over the columns of
@@ -664,18 +690,8 @@ inline size_t blk_off(const fpsq_band b, int64_t i, int64_t j) {  // block (i, j
 void band_solve(fpsq_band b) {
   hipStream_t s = b->stream;
   const int nb = (int)b->nb, bw = b->band_w - 1;
-  if (b->chain) {  // (both elimination chains advance side by side inside the one launch)
-    ChainArgs c{b->chain_pub, ++b->chain_seq, 0, nb, b->band_w, b->chain_safe, b->chain_bw, b->chain_err,
-                b->chain_pub + (size_t)nb * 512 + 1, 0};
-    c.pubseq = b->chain_break ? ~c.seq : c.seq;
-    c.ticket_base = (unsigned long long)(b->chain_seq - 1) * nb;
-    hipLaunchKernelGGL(k_trsv_chain<true>, dim3(nb), dim3(256), 0, s, b->Mb, kDB, b->invs, b->invsT, b->r2, b->y2, c);
-    c.seq = ++b->chain_seq;
-    c.pubseq = b->chain_break ? ~c.seq : c.seq;
-    c.ticket_base = (unsigned long long)(b->chain_seq - 1) * nb;
-    hipLaunchKernelGGL(k_trsv_chain<false>, dim3(nb), dim3(256), 0, s, b->Mb, kDB, b->invs, b->invsT, b->y2, b->r2, c);
-    return;
-  }
+  if (b->chain)  // (both elimination chains advance side by side inside the one launch)
+    return chain_sweeps(b, b->Mb, kDB, b->band_w, b->chain_safe, b->chain_bw);
   {
     int k0 = 0;
     const int cs = b->chain_safe, cb = b->chain_bw;
@@ -729,21 +745,7 @@ int band_finish(fpsq_band b, const double* a1, double* p1, double* q1, double* p
   else
     hipLaunchKernelGGL(k_dense_unpack2, dim3((unsigned)((b->m + 255) / 256)), dim3(256), 0, s, b->r2, b->o_q1, b->o_q2,
                        (int)b->m);
-  hipEventRecord(b->e1, s);
-  BCHK(b, hipMemcpyAsync(p1, b->o_p1, (size_t)b->n * 8, hipMemcpyDefault, s));
-  BCHK(b, hipMemcpyAsync(p2, b->o_p2, (size_t)b->n * 8, hipMemcpyDefault, s));
-  BCHK(b, hipMemcpyAsync(q1, b->o_q1, (size_t)b->m * 8, hipMemcpyDefault, s));
-  BCHK(b, hipMemcpyAsync(q2, b->o_q2, (size_t)b->m * 8, hipMemcpyDefault, s));
-  BCHK(b, hipStreamSynchronize(s));
-  if (b->chain_err && *b->chain_err) {
-    *b->chain_err = 0;
-    b->err = "triangular sweep: a block's solution did not arrive (bounded wait expired); FPSQ_TRSV_CHAIN=0 avoids the path";
-    return FPSQ_ERR_TIMEOUT;
-  }
-  float ms = 0.f;
-  hipEventElapsedTime(&ms, b->e0, b->e1);
-  b->info.last_solve_ms = ms;
-  return FPSQ_OK;
+  return solve_end(b, p1, q1, p2, q2, &b->info.last_solve_ms);
 }
 }  // namespace
 
@@ -805,20 +807,13 @@ int fpsq_band_analyze(int64_t n, int64_t m, const int32_t* rowptr, const int32_t
 
 int fpsq_band_destroy(fpsq_band b) {
   if (!b) return FPSQ_ERR_ARG;
-  hipSetDevice(b->device);
-  if (b->stream) hipStreamSynchronize(b->stream);
-  for (void* p : b->allocs) hipFree(p);
-  if (b->chain_err) hipHostFree(b->chain_err);
-  if (b->e0) hipEventDestroy(b->e0);
-  if (b->e1) hipEventDestroy(b->e1);
-  if (b->e2) hipEventDestroy(b->e2);
+  core_teardown(b);
   if (b->evA) hipEventDestroy(b->evA);
   if (b->evB) hipEventDestroy(b->evB);
   if (b->stream2) {
     hipStreamSynchronize(b->stream2);
     hipStreamDestroy(b->stream2);
   }
-  if (b->stream) hipStreamDestroy(b->stream);
   delete b;
   return FPSQ_OK;
 }
@@ -894,6 +889,7 @@ int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr
   for (int64_t c = 0; c < n; ++c)
     if (clast[c] >= 0) bwb = std::max<int64_t>(bwb, clast[c] / kDB - cfirst[c] / kDB);
   fpsq_band b = new fpsq_band_s();
+  b->name = "band";
   b->n = n;
   b->m = m;
   b->nnz = nnz;
@@ -944,35 +940,21 @@ int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr
     delete b;
     return FPSQ_ERR_HIP;
   }
-  hipEventCreate(&b->e0);
-  hipEventCreate(&b->e1);
-  hipEventCreate(&b->e2);
   hipStreamCreateWithFlags(&b->stream2, hipStreamNonBlocking);
   hipEventCreateWithFlags(&b->evA, hipEventDisableTiming);
   hipEventCreateWithFlags(&b->evB, hipEventDisableTiming);
-  int rc = 0;
+  int rc = core_setup(b, n);
   const size_t nz = (size_t)std::max<int64_t>(nnz, 1);
-  rc |= bmalloc(b, &b->rowptr, (size_t)m + 1) | bmalloc(b, &b->colind, nz) | bmalloc(b, &b->vals, nz);
-  rc |= bmalloc(b, &b->t_rowptr, (size_t)n + 1) | bmalloc(b, &b->t_colind, nz) | bmalloc(b, &b->t_vals, nz);
-  rc |= bmalloc(b, &b->t_perm, nz) | bmalloc(b, &b->rowspan, (size_t)m);
-  rc |= bmalloc(b, &b->Mb, (size_t)b->nb * b->band_w * kDB * kDB);
-  rc |= bmalloc(b, &b->invs, (size_t)b->nb * kDB * kDB) | bmalloc(b, &b->invsT, (size_t)b->nb * kDB * kDB);
-  rc |= bmalloc(b, &b->xn, (size_t)n * 2) | bmalloc(b, &b->atq, (size_t)n * 2);
-  rc |= bmalloc(b, &b->ym, (size_t)b->mpad * 2) | bmalloc(b, &b->r2, (size_t)b->mpad * 2) | bmalloc(b, &b->y2, (size_t)b->mpad * 2);
-  rc |= bmalloc(b, &b->in_a, (size_t)n) | bmalloc(b, &b->in_b, (size_t)std::max(n, b->mpad));
-  rc |= bmalloc(b, &b->o_p1, (size_t)n) | bmalloc(b, &b->o_p2, (size_t)n);
-  rc |= bmalloc(b, &b->o_q1, (size_t)b->mpad) | bmalloc(b, &b->o_q2, (size_t)b->mpad) | bmalloc(b, &b->info_dev, 4);
-  rc |= bmalloc(b, &b->chain_pub, (size_t)b->nb * 512 + 8);  // (+ the abort word)
-  if (!rc) hipMemset(b->chain_pub, 0, ((size_t)b->nb * 512 + 8) * 8);
-  if (hipHostMalloc((void**)&b->chain_err, 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) rc = 1;
-  else *b->chain_err = 0;
-  if (const char* e = getenv("FPSQ_TRSV_CHAIN")) b->chain = atoi(e) != 0;
-  if (const char* e = getenv("FPSQ_DEBUG_CHAIN_BREAK")) b->chain_break = atoi(e) != 0;
+  rc |= dalloc(b, &b->rowptr, (size_t)m + 1) | dalloc(b, &b->colind, nz) | dalloc(b, &b->vals, nz);
+  rc |= dalloc(b, &b->t_rowptr, (size_t)n + 1) | dalloc(b, &b->t_colind, nz) | dalloc(b, &b->t_vals, nz);
+  rc |= dalloc(b, &b->t_perm, nz) | dalloc(b, &b->rowspan, (size_t)m);
+  rc |= dalloc(b, &b->Mb, (size_t)b->nb * b->band_w * kDB * kDB);
+  rc |= dalloc(b, &b->xn, (size_t)n * 2) | dalloc(b, &b->atq, (size_t)n * 2) | dalloc(b, &b->ym, (size_t)b->mpad * 2);
   b->reordered = !rperm_h.empty();
   b->rperm_host = rperm_h;
   if (b->reordered)
-    rc |= bmalloc(b, &b->rperm, (size_t)m) | bmalloc(b, &b->vperm, nz) | bmalloc(b, &b->vals_in, nz) |
-          bmalloc(b, &b->in_bp, (size_t)b->mpad);
+    rc |= dalloc(b, &b->rperm, (size_t)m) | dalloc(b, &b->vperm, nz) | dalloc(b, &b->vals_in, nz) |
+          dalloc(b, &b->in_bp, (size_t)b->mpad);
   if (rc) {
     g_band_create_error = b->err;
     fpsq_band_destroy(b);
@@ -982,8 +964,6 @@ int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr
     hipMemcpy(b->rperm, rperm_h.data(), (size_t)m * 4, hipMemcpyHostToDevice);
     if (nnz > 0) hipMemcpy(b->vperm, vperm_h.data(), (size_t)nnz * 4, hipMemcpyHostToDevice);
   }
-  hipMemset(b->invs, 0, (size_t)b->nb * kDB * kDB * 8);  // k_potrf_inv128m writes the non-zero triangles only
-  hipMemset(b->invsT, 0, (size_t)b->nb * kDB * kDB * 8);
   hipMemcpy(b->rowptr, rp.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice);
   hipMemcpy(b->t_rowptr, tcnt.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice);
   hipMemcpy(b->rowspan, span.data(), (size_t)m * sizeof(int2), hipMemcpyHostToDevice);
@@ -1042,8 +1022,8 @@ int fpsq_band_create_coo(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, cons
   if (int rc = fpsq_band_create(out, n, m, rp.data(), scol.data(), device)) return rc;
   fpsq_band b = *out;
   const bool dup = ns != nnz;
-  if (bmalloc(b, &b->coo_perm, (size_t)std::max<int64_t>(nnz, 1)) || bmalloc(b, &b->coo_in, (size_t)std::max<int64_t>(nnz, 1)) ||
-      bmalloc(b, &b->csr_in, (size_t)std::max<int64_t>(ns, 1)) || (dup && bmalloc(b, &b->coo_slotptr, slotptr.size()))) {
+  if (dalloc(b, &b->coo_perm, (size_t)std::max<int64_t>(nnz, 1)) || dalloc(b, &b->coo_in, (size_t)std::max<int64_t>(nnz, 1)) ||
+      dalloc(b, &b->csr_in, (size_t)std::max<int64_t>(ns, 1)) || (dup && dalloc(b, &b->coo_slotptr, slotptr.size()))) {
     g_band_create_error = b->err;
     fpsq_band_destroy(b);
     *out = nullptr;
@@ -1062,20 +1042,12 @@ int fpsq_band_factorize_coo(fpsq_band b, const double* vals, double delta, int32
     return FPSQ_ERR_ARG;
   }
   hipSetDevice(b->device);
-  if (b->coo_nnz > 0) {
-    BCHK(b, hipMemcpyAsync(b->coo_in, vals, (size_t)b->coo_nnz * 8, hipMemcpyDefault, b->stream));
-    hipLaunchKernelGGL(k_coo_to_slots, dim3((unsigned)std::min<int64_t>((b->nnz + 255) / 256, 4096)), dim3(256), 0, b->stream,
-                       b->coo_in, b->coo_perm, b->coo_slotptr, (const int64_t*)nullptr, b->csr_in, b->nnz);
-  }
+  if (b->coo_nnz > 0)
+    if (int rc = coo_to_slots(b, vals, nullptr, b->csr_in, b->nnz)) return rc;
   return fpsq_band_factorize(b, b->csr_in, delta, info);  // (same stream: the slots are complete when it reads them)
 }
 
-int fpsq_band_set_regularization(fpsq_band b, double tol, double reg) {
-  if (!b || !(tol >= 0.0)) return FPSQ_ERR_ARG;
-  b->piv_tol = tol;
-  b->piv_reg = reg;
-  return FPSQ_OK;
-}
+int fpsq_band_set_regularization(fpsq_band b, double tol, double reg) { return set_regularization(b, tol, reg); }
 
 int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* info) {
   if (!b || (!vals && b->nnz > 0) || !(delta >= 0.0)) return FPSQ_ERR_ARG;
@@ -1085,17 +1057,17 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
   b->factored = false;
   if (b->nnz > 0) {
     if (b->reordered) {
-      BCHK(b, hipMemcpyAsync(b->vals_in, vals, (size_t)b->nnz * 8, hipMemcpyDefault, s));
+      CHK(b, hipMemcpyAsync(b->vals_in, vals, (size_t)b->nnz * 8, hipMemcpyDefault, s));
       hipLaunchKernelGGL(k_gather_d, dim3((unsigned)std::min<int64_t>((b->nnz + 255) / 256, 4096)), dim3(256), 0, s, b->vals_in,
                          b->vperm, b->vals, b->nnz);
     } else {
-      BCHK(b, hipMemcpyAsync(b->vals, vals, (size_t)b->nnz * 8, hipMemcpyDefault, s));
+      CHK(b, hipMemcpyAsync(b->vals, vals, (size_t)b->nnz * 8, hipMemcpyDefault, s));
     }
     hipLaunchKernelGGL(k_gather_d, dim3((unsigned)std::min<int64_t>((b->nnz + 255) / 256, 4096)), dim3(256), 0, s, b->vals,
                        b->t_perm, b->t_vals, b->nnz);
   }
-  BCHK(b, hipMemsetAsync(b->info_dev, 0, 8, s));
-  BCHK(b, hipMemsetAsync(b->Mb, 0, (size_t)nb * W * kDB * kDB * 8, s));
+  CHK(b, hipMemsetAsync(b->info_dev, 0, 8, s));
+  CHK(b, hipMemsetAsync(b->Mb, 0, (size_t)nb * W * kDB * kDB * 8, s));
   hipEventRecord(b->e0, s);
   // numeric phase 1: M = A A' + delta I into the band (jac_coord! + sparse(...) of src/solve_linear_system.jl:223-233)
   if (b->form_gen == 1)
@@ -1108,15 +1080,8 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
   // numeric phase 2: right-looking block-banded Cholesky (ldl_factorize!, :234), the dense back-end's block kernels.
   // One step: diagonal block k, panel blocks (k + st j, k) and trailing blocks (k + st i, k + st j), 1 <= j <= i <= rem
   // (st = 1: the whole band below k; st = 2: the blocks of k's own chain)
-  auto potrf = [&](hipStream_t q, int k) {
-    double* Mkk = b->Mb + blk_off(b, k, k);
-    double* inv = b->invs + (size_t)k * kDB * kDB;
-    hipLaunchKernelGGL(k_potrf_inv128m, dim3(1), dim3(kPotrfThreads5), kPotrfLds5, q, Mkk, kDB, inv, b->invsT + (size_t)k * kDB * kDB,
-                       k * kDB, b->info_dev, b->piv_tol, b->piv_reg);
-    return inv;
-  };
   auto step = [&](hipStream_t q, int k, int st, int rem) {
-    double* inv = potrf(q, k);
+    double* inv = launch_potrf(b, q, b->Mb + blk_off(b, k, k), kDB, k);
     if (rem <= 0) return;
     BlockStrides ps, ts;
     ps.on = ts.on = 1;
@@ -1143,34 +1108,17 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
     k0 = 2 * b->chain_safe;
   }
   for (int k = k0; k < nb; ++k) step(s, k, 1, std::min(bw, nb - 1 - k));
-  hipEventRecord(b->e2, s);
-  int32_t hinfo[2] = {0, 0};
-  BCHK(b, hipMemcpyAsync(hinfo, b->info_dev, 8, hipMemcpyDeviceToHost, s));
-  BCHK(b, hipStreamSynchronize(s));
-  float t0 = 0.f, t1 = 0.f;
-  hipEventElapsedTime(&t0, b->e0, b->e1);
-  hipEventElapsedTime(&t1, b->e1, b->e2);
-  b->info.last_form_ms = t0;
-  b->info.last_chol_ms = t1;
-  b->info.regularized_pivots = hinfo[1];
-  if (info)  // (first non-positive pivot, 1-based, in the CALLER's row numbering)
-    *info = hinfo[0] > 0 && b->reordered && hinfo[0] <= (int32_t)b->m ? b->rperm_host[hinfo[0] - 1] + 1 : hinfo[0];
-  b->factored = hinfo[0] == 0;
-  return hinfo[0] == 0 ? FPSQ_OK : 1;  // soft: not positive definite (factorized(str) == false, :242-246)
+  int32_t pivot = 0;
+  const int rc = factor_end(b, &b->info.last_form_ms, &b->info.last_chol_ms, &b->info.regularized_pivots, &pivot);
+  if (rc >= 0 && info)  // (first non-positive pivot, 1-based, in the CALLER's row numbering)
+    *info = pivot > 0 && b->reordered && pivot <= (int32_t)b->m ? b->rperm_host[pivot - 1] + 1 : pivot;
+  return rc;
 }
 
 int fpsq_band_solve_two_mixed(fpsq_band b, const double* rhs1, const double* rhs2, double* p1, double* q1, double* p2,
                               double* q2) {
-  if (!b || !rhs1 || !rhs2 || !p1 || !q1 || !p2 || !q2) return FPSQ_ERR_ARG;
-  if (!b->factored) {
-    b->err = "band_solve: no valid factorisation";
-    return FPSQ_ERR_STATE;
-  }
-  hipSetDevice(b->device);
+  if (int rc = solve_begin(b, true, rhs1, rhs2, p1, q1, p2, q2)) return rc;
   hipStream_t s = b->stream;
-  BCHK(b, hipMemcpyAsync(b->in_a, rhs1, (size_t)b->n * 8, hipMemcpyDefault, s));
-  BCHK(b, hipMemcpyAsync(b->in_b, rhs2, (size_t)b->m * 8, hipMemcpyDefault, s));
-  hipEventRecord(b->e0, s);
   // r = [A g, -c]:  q1 = M^-1 A g,  q2 = -M^-1 c;  then p1 = g - A'q1, p2 = -A'q2   
   hipLaunchKernelGGL(k_dense_pack2, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, s, b->in_a, 1.0,
                      (const double*)nullptr, 0.0, b->xn, (int)b->n, (int)b->n);
@@ -1188,16 +1136,8 @@ int fpsq_band_solve_two_mixed(fpsq_band b, const double* rhs1, const double* rhs
 
 int fpsq_band_solve_two_least_squares(fpsq_band b, const double* rhs1, const double* rhs2, double* p1, double* q1,
                                       double* p2, double* q2) {
-  if (!b || !rhs1 || !rhs2 || !p1 || !q1 || !p2 || !q2) return FPSQ_ERR_ARG;
-  if (!b->factored) {
-    b->err = "band_solve: no valid factorisation";
-    return FPSQ_ERR_STATE;
-  }
-  hipSetDevice(b->device);
+  if (int rc = solve_begin(b, false, rhs1, rhs2, p1, q1, p2, q2)) return rc;
   hipStream_t s = b->stream;
-  BCHK(b, hipMemcpyAsync(b->in_a, rhs1, (size_t)b->n * 8, hipMemcpyDefault, s));
-  BCHK(b, hipMemcpyAsync(b->in_b, rhs2, (size_t)b->n * 8, hipMemcpyDefault, s));
-  hipEventRecord(b->e0, s);
   hipLaunchKernelGGL(k_dense_pack2, dim3((unsigned)((b->n + 255) / 256)), dim3(256), 0, s, b->in_a, 1.0, b->in_b, 1.0, b->xn,
                      (int)b->n, (int)b->n);
   hipLaunchKernelGGL(k_csr_mv2, dim3((unsigned)((b->m + 255) / 256)), dim3(256), 0, s, b->rowptr, b->colind, b->vals, b->xn,
@@ -1212,11 +1152,4 @@ int fpsq_band_get_info(fpsq_band b, fpsq_band_info* info) {
   *info = b->info;
   return FPSQ_OK;
 }
-
-int fpsq_dense_get_info(fpsq_dense d, fpsq_dense_info* info) {
-  if (!d || !info) return FPSQ_ERR_ARG;
-  *info = d->info;
-  return FPSQ_OK;
-}
-
 }  // extern "C"

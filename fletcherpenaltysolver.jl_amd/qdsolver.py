@@ -174,26 +174,11 @@ class HIPQDSolver(QDSolver):
 qdsolver_correspondence = {"hip": HIPQDSolver}
 
 
-class HIPDirectQDSolver(QDSolver):
-    """`HIPDirectQDSolver(nlp, T(0))`: the DIRECT back-end on the MI355X for small / dense Jacobians -- the role
-    `LDLtSolver` plays in the reference (src/solve_two_systems_struct.jl:299-353; it is the reference's default,
-    src/parameters.jl:290).  Instead of an LDL' of K it factorises the normal equations M = A A' + delta I (fp64 MFMA
-    SYRK + blocked Cholesky) and solves both systems with two right-hand sides; like `ldl_factorize!` it refactorises
-    on every `solve_two_mixed` (src/solve_linear_system.jl:233-234) and re-uses the factors in
-    `solve_two_least_squares` (:194-195).  A non positive definite M only warns (:244-246).
-    Keywords of `LDLtSolver` (struct.jl:308-316): ldlt_tol (sqrt(eps)) and ldlt_r2 drive the DYNAMIC REGULARISATION of
-    the factorisation; ldlt_r1 concerns the identity block of K, whose pivots are 1 and never regularised.  A pivot of M
-    not above ldlt_tol marks a constraint row that depends linearly on the earlier ones at working precision.
-    * ldlt_r2 (default -sqrt(eps), the reference's `LDLtSolver` default, struct.jl:314): the pivot is replaced by -ldlt_r2 --
-      the value LDLFactorizations.jl puts in the (2,2) block of K.
-    * ldlt_r2 = "drop" (or -REG_DROP): the pivot is DROPPED instead (FPSQ_REG_DROP = 1e200: that row's multiplier comes out
-      as zero, the basic solution of the consistent normal equations).  An OPTION, not the default: the reference's
-      -sqrt(eps) acts on pivots of K in a fill-reducing order (on FLT, test/test-2.jl:264-287, AMD eliminates both
-      constraint nodes first, which amounts to the uniform shift M + sqrt(eps) I); the same number on a pivot of M in
-      natural order is not the same rule, and either way the multiplier estimates grow like 1 / sqrt(eps) on an
-      inconsistent right-hand side (phi ~ 1e10 at FLT's x0: a Newton-CG sub-solver crawls).  Dropping keeps them bounded
-      like the exact back-end's minimum-norm solve.
-    Dense storage: m <= 65536."""
+class _DirectQDSolver(QDSolver):
+    """What the two direct back-ends share: the constructor contract of `LDLtSolver`, the solves on the cached factor and the
+    lazy restore of the delta factor.  A back-end supplies `_prefix` (its entry points are fpsq_<prefix>_*), `_Info`,
+    `_create(rows, cols, device)` (sets the handle `_h` up with the COO structure; raises FpsqError) and
+    `_hand_over(vals, delta, info)` (values to the device and factorisation; returns the library's code)."""
 
     def __init__(self, nlp, _zero=0.0, *, explicit_linear_constraints=False, ldlt_tol=None, ldlt_r1=None, ldlt_r2=None,
                  **kwargs):
@@ -203,33 +188,32 @@ class HIPDirectQDSolver(QDSolver):
         self.explicit_linear_constraints = bool(explicit_linear_constraints)
         self._lib = _lib.load()
         self.nvar, self.ncon = int(nlp.meta.nvar), int(nlp.meta.ncon)
-        d = C.c_void_p()
-        if self._lib.fpsq_dense_create(C.byref(d), self.nvar, self.ncon, int(kwargs.get("device", 0))) != 0:
-            raise FpsqError(self._lib.fpsq_dense_last_error(None).decode())
-        self._d = d
-        # jac_structure! once (struct.jl:331-337): the COO pattern stays on the device, sorted; per x only the output of
-        # jac_coord! crosses the boundary (host or device memory) -- no dense array, no re-ordering on the host
+        # jac_structure! once (struct.jl:331-337), in the model's COO order (1-based, duplicates allowed): the library sorts it
+        # and keeps the order on the device; per x only the output of jac_coord! crosses the boundary (host or device memory)
         rows, cols = nlp.jac_structure()
         rows = np.ascontiguousarray(rows, dtype=np.int64)
         cols = np.ascontiguousarray(cols, dtype=np.int64)
-        self._check(self._lib.fpsq_dense_set_structure_coo(d, rows.size, rows.ctypes.data, cols.ctypes.data, 1))
+        self._create(rows, cols, int(kwargs.get("device", 0)))
         self.factorized = False
         se = float(np.sqrt(np.finfo(float).eps))
         self.ldlt_tol = se if ldlt_tol is None else float(ldlt_tol)        # struct.jl:312
-        self.ldlt_r2 = _ldlt_r2(ldlt_r2)                                   # struct.jl:314: -sqrt(eps) unless given ("drop": see the docstring)
-        self._check(self._lib.fpsq_dense_set_regularization(self._d, self.ldlt_tol, -self.ldlt_r2))
+        self.ldlt_r2 = _ldlt_r2(ldlt_r2)                                   # struct.jl:314: -sqrt(eps) unless given ("drop": see HIPDirectQDSolver)
+        self._check(self._fn("set_regularization")(self._h, self.ldlt_tol, -self.ldlt_r2))
         self._fact_key = None
         self._owed = self._mixed_at = None
 
+    def _fn(self, name):
+        return getattr(self._lib, f"fpsq_{self._prefix}_{name}")
+
     def _check(self, rc):
         if rc < 0:
-            raise FpsqError(self._lib.fpsq_dense_last_error(self._d).decode())
+            raise FpsqError(self._fn("last_error")(self._h).decode())
         return rc
 
     def close(self):
-        if getattr(self, "_d", None):
-            self._lib.fpsq_dense_destroy(self._d)
-            self._d = None
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
 
     def __del__(self):
         try:
@@ -240,14 +224,12 @@ class HIPDirectQDSolver(QDSolver):
     def _factorize(self, nlp, x, delta=None):
         delta = float(nlp.delta if delta is None else delta)
         vals = _coord_values(nlp.pen.jac_coord(x))                                     # linear_system.jl:223-228
-        self._check(self._lib.fpsq_dense_set_jacobian_coo(self._d, _lib.ptr(vals)))
-        info = C.c_int32()
-        rc = self._check(self._lib.fpsq_dense_factorize(self._d, delta, C.byref(info)))
+        rc = self._hand_over(vals, delta, C.c_int32())
         self.factorized = rc == 0
         self._fact_key = (np.asarray(x, dtype=np.float64).tobytes(), delta) if rc == 0 else None
         return rc
 
-    def _solve(self, fn, rhs1, rhs2):
+    def _solve(self, name, rhs1, rhs2):
         n, m = self.nvar, self.ncon
         rhs1 = np.ascontiguousarray(rhs1, dtype=np.float64)
         rhs2 = np.ascontiguousarray(rhs2, dtype=np.float64)
@@ -255,18 +237,18 @@ class HIPDirectQDSolver(QDSolver):
         if not self.factorized:
             warnings.warn("_solve_ldlt_factorization: failed _factorization")
             return p1, q1, p2, q2
-        self._check(fn(self._d, rhs1.ctypes.data, rhs2.ctypes.data, p1.ctypes.data, q1.ctypes.data, p2.ctypes.data,
-                       q2.ctypes.data))
+        self._check(self._fn(name)(self._h, rhs1.ctypes.data, rhs2.ctypes.data, p1.ctypes.data, q1.ctypes.data,
+                                   p2.ctypes.data, q2.ctypes.data))
         return p1, q1, p2, q2
 
     def solve_two_mixed(self, nlp, x, rhs1, rhs2):
         self._factorize(nlp, x)
         self._owed, self._mixed_at = None, (np.array(x, dtype=np.float64), float(nlp.delta))
-        return self._solve(self._lib.fpsq_dense_solve_two_mixed, rhs1, rhs2)
+        return self._solve("solve_two_mixed", rhs1, rhs2)
 
     def solve_two_least_squares(self, nlp, x, rhs1, rhs2):
         self._restore_factor(nlp)
-        return self._solve(self._lib.fpsq_dense_solve_two_least_squares, rhs1, rhs2)
+        return self._solve("solve_two_least_squares", rhs1, rhs2)
 
     def _restore_factor(self, nlp):
         """solve_two_extras may have left the factor of A A' + tau I (tau != delta) in the handle; the reference's extras never
@@ -289,114 +271,72 @@ class HIPDirectQDSolver(QDSolver):
             if tau != float(nlp.delta) and self._owed is None and self._mixed_at is not None:
                 self._owed = self._mixed_at  # (the factor a later solve_two_least_squares is entitled to: restored lazily)
             self._factorize(nlp, x, tau)
-        _, q1, _, q2 = self._solve(self._lib.fpsq_dense_solve_two_mixed, rhs1, rhs2)
+        _, q1, _, q2 = self._solve("solve_two_mixed", rhs1, rhs2)
         return q1, -q2
 
     def info(self):
-        i = _lib.DenseInfo()
-        self._check(self._lib.fpsq_dense_get_info(self._d, C.byref(i)))
+        i = self._Info()
+        self._check(self._fn("get_info")(self._h, C.byref(i)))
         return i.as_dict()
+
+
+class HIPDirectQDSolver(_DirectQDSolver):
+    """`HIPDirectQDSolver(nlp, T(0))`: the DIRECT back-end on the MI355X for small / dense Jacobians -- the role
+    `LDLtSolver` plays in the reference (src/solve_two_systems_struct.jl:299-353; it is the reference's default,
+    src/parameters.jl:290).  Instead of an LDL' of K it factorises the normal equations M = A A' + delta I (fp64 MFMA
+    SYRK + blocked Cholesky) and solves both systems with two right-hand sides; like `ldl_factorize!` it refactorises
+    on every `solve_two_mixed` (src/solve_linear_system.jl:233-234) and re-uses the factors in
+    `solve_two_least_squares` (:194-195).  A non positive definite M only warns (:244-246).
+    Keywords of `LDLtSolver` (struct.jl:308-316): ldlt_tol (sqrt(eps)) and ldlt_r2 drive the DYNAMIC REGULARISATION of
+    the factorisation; ldlt_r1 concerns the identity block of K, whose pivots are 1 and never regularised.  A pivot of M
+    not above ldlt_tol marks a constraint row that depends linearly on the earlier ones at working precision.
+    * ldlt_r2 (default -sqrt(eps), the reference's `LDLtSolver` default, struct.jl:314): the pivot is replaced by -ldlt_r2 --
+      the value LDLFactorizations.jl puts in the (2,2) block of K.
+    * ldlt_r2 = "drop" (or -REG_DROP): the pivot is DROPPED instead (FPSQ_REG_DROP = 1e200: that row's multiplier comes out
+      as zero, the basic solution of the consistent normal equations).  An OPTION, not the default: the reference's
+      -sqrt(eps) acts on pivots of K in a fill-reducing order (on FLT, test/test-2.jl:264-287, AMD eliminates both
+      constraint nodes first, which amounts to the uniform shift M + sqrt(eps) I); the same number on a pivot of M in
+      natural order is not the same rule, and either way the multiplier estimates grow like 1 / sqrt(eps) on an
+      inconsistent right-hand side (phi ~ 1e10 at FLT's x0: a Newton-CG sub-solver crawls).  Dropping keeps them bounded
+      like the exact back-end's minimum-norm solve.
+    Dense storage: m <= 65536."""
+
+    _prefix, _Info = "dense", _lib.DenseInfo
+
+    def _create(self, rows, cols, device):
+        d = C.c_void_p()
+        if self._lib.fpsq_dense_create(C.byref(d), self.nvar, self.ncon, device) != 0:
+            raise FpsqError(self._lib.fpsq_dense_last_error(None).decode())
+        self._h = d
+        self._check(self._lib.fpsq_dense_set_structure_coo(d, rows.size, rows.ctypes.data, cols.ctypes.data, 1))
+
+    def _hand_over(self, vals, delta, info):
+        self._check(self._lib.fpsq_dense_set_jacobian_coo(self._h, _lib.ptr(vals)))
+        return self._check(self._lib.fpsq_dense_factorize(self._h, delta, C.byref(info)))
 
 
 qdsolver_correspondence["hip_direct"] = HIPDirectQDSolver
 
 
-class HIPBandedDirectQDSolver(QDSolver):
+class HIPBandedDirectQDSolver(_DirectQDSolver):
     """`HIPBandedDirectQDSolver(nlp, T(0))`: the DIRECT back-end for SPARSE Jacobians whose normal-equations matrix is
     banded (PDE-like models) -- `LDLtSolver`'s role at sizes where a dense M does not fit (include/fpsq.h, fpsq_band_*).
     The constructor is the symbolic phase (struct.jl:326-344), `solve_two_mixed` refactorises at x
     (solve_linear_system.jl:223-234), `solve_two_least_squares` re-uses the factor (:194-195); ldlt_tol / ldlt_r2 as in
     HIPDirectQDSolver."""
 
-    def __init__(self, nlp, _zero=0.0, *, explicit_linear_constraints=False, ldlt_tol=None, ldlt_r1=None, ldlt_r2=None,
-                 **kwargs):
-        if explicit_linear_constraints:
-            from .nlpmodels import NonlinearConstraintsView
-            nlp = NonlinearConstraintsView(nlp)
-        self.explicit_linear_constraints = bool(explicit_linear_constraints)
-        self._lib = _lib.load()
-        self.nvar, self.ncon = int(nlp.meta.nvar), int(nlp.meta.ncon)
-        # jac_structure! once (struct.jl:331-337), in the model's COO order (1-based, duplicates allowed): sorted into CSR
-        # slots by the library, the order kept on the device
-        rows, cols = nlp.jac_structure()
-        rows = np.ascontiguousarray(rows, dtype=np.int64)
-        cols = np.ascontiguousarray(cols, dtype=np.int64)
+    _prefix, _Info = "band", _lib.BandInfo
+
+    def _create(self, rows, cols, device):
         b = C.c_void_p()
         rc = self._lib.fpsq_band_create_coo(C.byref(b), self.nvar, self.ncon, rows.size, rows.ctypes.data, cols.ctypes.data,
-                                            1, int(kwargs.get("device", 0)))
+                                            1, device)
         if rc != 0:
             raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
-        self._b = b
-        se = float(np.sqrt(np.finfo(float).eps))
-        self.ldlt_tol = se if ldlt_tol is None else float(ldlt_tol)
-        self.ldlt_r2 = _ldlt_r2(ldlt_r2)                                   # (struct.jl:314; "drop": see HIPDirectQDSolver)
-        self._check(self._lib.fpsq_band_set_regularization(b, self.ldlt_tol, -self.ldlt_r2))
-        self._owed = self._mixed_at = None
-        self.factorized = False
-        self._fact_key = None
+        self._h = b
 
-    def _check(self, rc):
-        if rc < 0:
-            raise FpsqError(self._lib.fpsq_band_last_error(self._b).decode())
-        return rc
-
-    def close(self):
-        if getattr(self, "_b", None):
-            self._lib.fpsq_band_destroy(self._b)
-            self._b = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _factorize(self, nlp, x, delta=None):
-        delta = float(nlp.delta if delta is None else delta)
-        vals = _coord_values(nlp.pen.jac_coord(x))                                     # linear_system.jl:223-228
-        info = C.c_int32()
-        rc = self._check(self._lib.fpsq_band_factorize_coo(self._b, _lib.ptr(vals), delta, C.byref(info)))
-        self.factorized = rc == 0
-        self._fact_key = (np.asarray(x, dtype=np.float64).tobytes(), delta) if rc == 0 else None
-        return rc
-
-    def _solve(self, fn, rhs1, rhs2):
-        n, m = self.nvar, self.ncon
-        rhs1 = np.ascontiguousarray(rhs1, dtype=np.float64)
-        rhs2 = np.ascontiguousarray(rhs2, dtype=np.float64)
-        p1, q1, p2, q2 = np.zeros(n), np.zeros(m), np.zeros(n), np.zeros(m)
-        if not self.factorized:
-            warnings.warn("_solve_ldlt_factorization: failed _factorization")
-            return p1, q1, p2, q2
-        self._check(fn(self._b, rhs1.ctypes.data, rhs2.ctypes.data, p1.ctypes.data, q1.ctypes.data, p2.ctypes.data,
-                       q2.ctypes.data))
-        return p1, q1, p2, q2
-
-    def solve_two_mixed(self, nlp, x, rhs1, rhs2):
-        self._factorize(nlp, x)
-        self._owed, self._mixed_at = None, (np.array(x, dtype=np.float64), float(nlp.delta))
-        return self._solve(self._lib.fpsq_band_solve_two_mixed, rhs1, rhs2)
-
-    def solve_two_least_squares(self, nlp, x, rhs1, rhs2):
-        if self._owed is not None:  # (the factor of delta, displaced by solve_two_extras: see HIPDirectQDSolver._restore_factor)
-            x0, delta = self._owed
-            self._owed = None
-            self._factorize(nlp, x0, delta)
-        return self._solve(self._lib.fpsq_band_solve_two_least_squares, rhs1, rhs2)
-
-    def solve_two_extras(self, nlp, x, rhs1, rhs2):
-        tau = max(float(nlp.delta), 1e-14)                                            # solve_linear_system.jl:148
-        if self._fact_key != (np.asarray(x, dtype=np.float64).tobytes(), tau):
-            if tau != float(nlp.delta) and self._owed is None and self._mixed_at is not None:
-                self._owed = self._mixed_at
-            self._factorize(nlp, x, tau)
-        _, q1, _, q2 = self._solve(self._lib.fpsq_band_solve_two_mixed, rhs1, rhs2)
-        return q1, -q2
-
-    def info(self):
-        i = _lib.BandInfo()
-        self._check(self._lib.fpsq_band_get_info(self._b, C.byref(i)))
-        return i.as_dict()
+    def _hand_over(self, vals, delta, info):
+        return self._check(self._lib.fpsq_band_factorize_coo(self._h, _lib.ptr(vals), delta, C.byref(info)))
 
 
 qdsolver_correspondence["hip_ldlt"] = HIPBandedDirectQDSolver
