@@ -39,6 +39,12 @@ struct DirectCore {
   int64_t coo_nnz = -1;
   int32_t *coo_perm = nullptr, *coo_slotptr = nullptr;
   double* coo_in = nullptr;
+  // device-resident evaluations (fpsq_band_qp_*): the caller's producer stream (include/fpsq.h "INPUT READINESS") and the
+  // scalars of a call, device side and pinned host side
+  bool in_stream_on = false;
+  hipStream_t in_stream = nullptr;
+  hipEvent_t ev_in = nullptr;
+  double *scal = nullptr, *scal_host = nullptr;
   std::vector<void*> allocs;
 };
 
@@ -132,6 +138,8 @@ void core_teardown(DirectCore* c) {
   if (c->stream) hipStreamSynchronize(c->stream);
   for (void* p : c->allocs) hipFree(p);
   if (c->chain_err) hipHostFree(c->chain_err);
+  if (c->scal_host) hipHostFree(c->scal_host);
+  if (c->ev_in) hipEventDestroy(c->ev_in);
   if (c->e0) hipEventDestroy(c->e0);
   if (c->e1) hipEventDestroy(c->e1);
   if (c->e2) hipEventDestroy(c->e2);
@@ -233,6 +241,103 @@ int solve_end(DirectCore* c, double* p1, double* q1, double* p2, double* q2, dou
   *solve_ms = ms;
   return FPSQ_OK;
 }
+
+// ---- around the kernels of a device-resident evaluation (fpsq_band_qp_*); nothing here knows how M is stored
+
+int set_input_stream(DirectCore* c, int32_t enabled, void* hip_stream) {
+  if (!c) return FPSQ_ERR_ARG;
+  hipSetDevice(c->device);
+  if (enabled && !c->ev_in) CHK(c, hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming));
+  c->in_stream_on = enabled != 0;
+  c->in_stream = (hipStream_t)hip_stream;
+  return FPSQ_OK;
+}
+
+// the handle's stream waits (event, no host block) for everything enqueued so far on the registered stream
+int wait_input(DirectCore* c) {
+  if (!c->in_stream_on) return FPSQ_OK;
+  CHK(c, hipEventRecord(c->ev_in, c->in_stream));
+  CHK(c, hipStreamWaitEvent(c->stream, c->ev_in, 0));
+  return FPSQ_OK;
+}
+
+// true when p is device memory of the handle's GPU (kernels then use it in place)
+bool on_device(const DirectCore* c, const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // plain host memory: not an error
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice && a.device == c->device;
+}
+
+// An input vector as the kernels read it: in place when it lives on the handle's GPU, else copied into `stage`
+int arg_in(DirectCore* c, const double* p, double* stage, size_t len, const double** out) {
+  *out = p;
+  if (!p || on_device(c, p)) return FPSQ_OK;
+  CHK(c, hipMemcpyAsync(stage, p, len * 8, hipMemcpyDefault, c->stream));
+  *out = stage;
+  return FPSQ_OK;
+}
+
+// ... where they write an output vector (null stays null), and the copy back of one that was staged
+double* arg_out(DirectCore* c, double* p, double* stage) { return !p || on_device(c, p) ? p : stage; }
+
+int arg_back(DirectCore* c, double* p, const double* wrote, size_t len) {
+  if (!p || wrote == p) return FPSQ_OK;
+  CHK(c, hipMemcpyAsync(p, wrote, len * 8, hipMemcpyDefault, c->stream));
+  return FPSQ_OK;
+}
+
+// Start of an evaluation on the cached factor: state check, input ordering, e0
+int eval_begin(DirectCore* c) {
+  if (!c->factored) {
+    c->err = std::string(c->name) + "_solve: no valid factorisation";
+    return FPSQ_ERR_STATE;
+  }
+  hipSetDevice(c->device);
+  if (int rc = wait_input(c)) return rc;
+  hipEventRecord(c->e0, c->stream);
+  return FPSQ_OK;
+}
+
+// ... and its end: e1, the one device-to-host transfer of the call's `nscal` scalars (c->scal -> c->scal_host), the
+// synchronisation that makes the outputs complete, the check of the sweeps' error word
+int eval_end(DirectCore* c, int nscal, double* solve_ms) {
+  hipStream_t s = c->stream;
+  hipEventRecord(c->e1, s);
+  if (nscal > 0) CHK(c, hipMemcpyAsync(c->scal_host, c->scal, (size_t)nscal * 8, hipMemcpyDeviceToHost, s));
+  CHK(c, hipStreamSynchronize(s));
+  if (c->chain_err && *c->chain_err) {
+    *c->chain_err = 0;
+    c->err = "triangular sweep: a block's solution did not arrive (bounded wait expired); FPSQ_TRSV_CHAIN=0 avoids the path";
+    return FPSQ_ERR_TIMEOUT;
+  }
+  float ms = 0.f;
+  hipEventElapsedTime(&ms, c->e0, c->e1);
+  *solve_ms = ms;
+  return FPSQ_OK;
+}
+
+// lanes that share a row in the product kernels of the evaluations: the largest power of two <= the mean row length, 1 .. 64
+int lane_group(int64_t nnz, int64_t rows) {
+  const int64_t mean = rows > 0 ? nnz / rows : 1;
+  int lg = 1;
+  while (lg < 64 && 2 * lg <= mean) lg *= 2;
+  return lg;
+}
+
+// runs the statement(s) with the compile-time constant LG = lg (a value lane_group returns)
+#define WITH_LANE_GROUP(lg, ...)                            \
+  switch (lg) {                                             \
+    case 1: { constexpr int LG = 1; __VA_ARGS__; } break;    \
+    case 2: { constexpr int LG = 2; __VA_ARGS__; } break;    \
+    case 4: { constexpr int LG = 4; __VA_ARGS__; } break;    \
+    case 8: { constexpr int LG = 8; __VA_ARGS__; } break;    \
+    case 16: { constexpr int LG = 16; __VA_ARGS__; } break;  \
+    case 32: { constexpr int LG = 32; __VA_ARGS__; } break;  \
+    default: { constexpr int LG = 64; __VA_ARGS__; } break;  \
+  }
 }  // namespace
 
 // ===================================================================================================== dense M
@@ -517,7 +622,20 @@ struct fpsq_band_s : DirectCore {
   hipStream_t stream2 = nullptr;  // the second elimination chain
   hipEvent_t evA = nullptr, evB = nullptr;
   double* csr_in = nullptr;  // fpsq_band_create_coo: the CSR slots the sorted COO entries are summed into
+  bool have_vals = false;    // a factorisation has put the Jacobian's values into vals / t_vals (fpsq_band_jac_mul, fpsq_band_qp_*)
   fpsq_band_info info{};
+};
+
+// fpsq_band_qp_create: the model's vectors on the handle's device and what an evaluation needs besides the handle's own
+// buffers (which it borrows: in_a / in_b / o_p1 / o_p2 / o_q1 stage host-resident arguments, xn holds the packed
+// right-hand sides of the A product, o_q2 keeps c resp. A v between the two product kernels)
+struct fpsq_band_qp_s {
+  fpsq_band b = nullptr;
+  double *q = nullptr, *d = nullptr, *bp = nullptr;  // n, n, m (b in the STORED row order)
+  double *partP = nullptr, *partE = nullptr;         // per-workgroup partial sums of the two product kernels, [grid][2]
+  int lgA = 1, lgT = 1;                              // lanes per row of A / of A' (lane_group)
+  int gridP = 1, gridE = 1;
+  bool gather_g = false;  // FPSQ_BAND_QP_G=1: g formed at gather time instead of by k_bq_pack (A/B runs)
 };
 
 namespace {
@@ -1042,6 +1160,7 @@ int fpsq_band_factorize_coo(fpsq_band b, const double* vals, double delta, int32
     return FPSQ_ERR_ARG;
   }
   hipSetDevice(b->device);
+  if (int rc = wait_input(b)) return rc;
   if (b->coo_nnz > 0)
     if (int rc = coo_to_slots(b, vals, nullptr, b->csr_in, b->nnz)) return rc;
   return fpsq_band_factorize(b, b->csr_in, delta, info);  // (same stream: the slots are complete when it reads them)
@@ -1055,6 +1174,8 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
   hipStream_t s = b->stream;
   const int nb = (int)b->nb, W = b->band_w, bw = W - 1;
   b->factored = false;
+  if (int rc = wait_input(b)) return rc;  // (device-resident values produced on a stream registered with fpsq_band_set_input_stream)
+  b->have_vals = true;
   if (b->nnz > 0) {
     if (b->reordered) {
       CHK(b, hipMemcpyAsync(b->vals_in, vals, (size_t)b->nnz * 8, hipMemcpyDefault, s));
@@ -1150,6 +1271,162 @@ int fpsq_band_solve_two_least_squares(fpsq_band b, const double* rhs1, const dou
 int fpsq_band_get_info(fpsq_band b, fpsq_band_info* info) {
   if (!b || !info) return FPSQ_ERR_ARG;
   *info = b->info;
+  return FPSQ_OK;
+}
+}  // extern "C"
+
+// ------------------------------------------------------------- device-resident eq-QP evaluations on the banded handle
+
+namespace {
+constexpr int kBqMaxGrid = 2048;  // workgroups of a product kernel: 256 CUs x 8 resident workgroups of 256 threads
+
+int bq_grid(int64_t rows, int lg) { return (int)std::min<int64_t>((rows + 256 / lg - 1) / (256 / lg), kBqMaxGrid); }
+
+// The launches between the arguments and the outputs of an evaluation, left in flight on b->stream: [pack,] the A product
+// that writes the right-hand sides of the M-solves where the sweeps read them, the sweeps, the A' product with the row
+// epilogue.  hp: hprod (x = v, out = Hv), else objgrad (out = grad phi).  All pointers are device pointers.
+void bq_launches(fpsq_band b, fpsq_band_qp qp, bool hp, const double* x, const double* xk, double sigma, double rho,
+                 double eta, double* out, double* gs, double* ys) {
+  hipStream_t s = b->stream;
+  const int n = (int)b->n, m = (int)b->m, mpad = (int)b->mpad;
+  double* keep = b->o_q2;
+  if (!qp->gather_g) {
+    if (hp)
+      hipLaunchKernelGGL(k_bq_pack<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, qp->q, qp->d, b->xn, n);
+    else
+      hipLaunchKernelGGL(k_bq_pack<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, qp->q, qp->d, b->xn, n);
+  }
+#define BQ_PROLOGUE(HP, GM)                                                                                              \
+  hipLaunchKernelGGL((k_bq_prologue<LG, HP, GM>), dim3(qp->gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, b->xn, x, \
+                     qp->q, qp->d, qp->bp, b->r2, keep, qp->partP, m, mpad, n)
+  WITH_LANE_GROUP(qp->lgA, if (hp) {
+    if (qp->gather_g) BQ_PROLOGUE(true, true);
+    else BQ_PROLOGUE(true, false);
+  } else {
+    if (qp->gather_g) BQ_PROLOGUE(false, true);
+    else BQ_PROLOGUE(false, false);
+  })
+#undef BQ_PROLOGUE
+  band_solve(b);
+#define BQ_EPILOGUE(HP)                                                                                                   \
+  hipLaunchKernelGGL((k_bq_epilogue<LG, HP>), dim3(qp->gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, b->r2,   \
+                     keep, b->reordered ? b->rperm : (const int32_t*)nullptr, x, xk, qp->q, qp->d, sigma, rho, eta, out, gs, \
+                     ys, qp->partE, n, m)
+  WITH_LANE_GROUP(qp->lgT, if (hp) BQ_EPILOGUE(true); else BQ_EPILOGUE(false);)
+#undef BQ_EPILOGUE
+}
+}  // namespace
+
+extern "C" {
+
+int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void* hip_stream) {
+  return set_input_stream(b, enabled, hip_stream);
+}
+
+int fpsq_band_qp_create(fpsq_band b, const double* qdiag, const double* d, const double* bvec, fpsq_band_qp* out) {
+  if (!b || !qdiag || !d || !bvec || !out) return FPSQ_ERR_ARG;
+  hipSetDevice(b->device);
+  if (!b->scal) {  // the scalars of a call: device side and pinned host side
+    if (dalloc(b, &b->scal, 8)) return FPSQ_ERR_HIP;
+    CHK(b, hipHostMalloc((void**)&b->scal_host, 64, hipHostMallocDefault));
+  }
+  std::vector<double> bh((size_t)b->m), bs((size_t)b->m);
+  CHK(b, hipMemcpy(bh.data(), bvec, (size_t)b->m * 8, hipMemcpyDefault));
+  for (int64_t p = 0; p < b->m; ++p) bs[p] = bh[b->reordered ? b->rperm_host[p] : p];
+  fpsq_band_qp qp = new fpsq_band_qp_s();
+  qp->b = b;
+  qp->lgA = lane_group(b->nnz, b->m);
+  qp->lgT = lane_group(b->nnz, b->n);
+  qp->gridP = bq_grid(b->mpad, qp->lgA);
+  qp->gridE = bq_grid(b->n, qp->lgT);
+  if (const char* e = getenv("FPSQ_BAND_QP_G")) qp->gather_g = atoi(e) != 0;
+  const size_t nb8 = (size_t)b->n * 8, mb8 = (size_t)b->m * 8;
+  if (hipMalloc((void**)&qp->q, nb8) != hipSuccess || hipMalloc((void**)&qp->d, nb8) != hipSuccess ||
+      hipMalloc((void**)&qp->bp, mb8) != hipSuccess || hipMalloc((void**)&qp->partP, (size_t)qp->gridP * 16) != hipSuccess ||
+      hipMalloc((void**)&qp->partE, (size_t)qp->gridE * 16) != hipSuccess ||
+      hipMemcpy(qp->q, qdiag, nb8, hipMemcpyDefault) != hipSuccess || hipMemcpy(qp->d, d, nb8, hipMemcpyDefault) != hipSuccess ||
+      hipMemcpy(qp->bp, bs.data(), mb8, hipMemcpyHostToDevice) != hipSuccess) {
+    b->err = "band_qp_create: cannot allocate or fill the model's vectors";
+    fpsq_band_qp_destroy(qp);
+    return FPSQ_ERR_HIP;
+  }
+  *out = qp;
+  return FPSQ_OK;
+}
+
+int fpsq_band_qp_destroy(fpsq_band_qp qp) {
+  if (!qp) return FPSQ_ERR_ARG;
+  for (double* p : {qp->q, qp->d, qp->bp, qp->partP, qp->partE})
+    if (p) hipFree(p);
+  delete qp;
+  return FPSQ_OK;
+}
+
+int fpsq_band_qp_objgrad(fpsq_band b, fpsq_band_qp qp, const double* x, double sigma, double rho, double eta, const double* xk,
+                         double* fx, double* gx, double* ys, double* gs) {
+  if (!b || !qp || qp->b != b || !x || !fx) return FPSQ_ERR_ARG;
+  if (int rc = eval_begin(b)) return rc;
+  rho = rho > 0.0 ? rho : 0.0;  // (the reference adds these terms only when the parameter is positive)
+  eta = eta > 0.0 ? eta : 0.0;
+  const size_t n = (size_t)b->n, m = (size_t)b->m;
+  const double *dx = nullptr, *dxk = nullptr;
+  if (int rc = arg_in(b, x, b->in_a, n, &dx)) return rc;
+  if (int rc = arg_in(b, eta > 0.0 ? xk : nullptr, b->in_b, n, &dxk)) return rc;
+  double *dgx = arg_out(b, gx, b->o_p1), *dgs = arg_out(b, gs, b->o_p2), *dys = arg_out(b, ys, b->o_q1);
+  bq_launches(b, qp, false, dx, dxk, sigma, rho, eta, dgx, dgs, dys);
+  hipLaunchKernelGGL(k_bq_phi, dim3(1), dim3(256), 0, b->stream, qp->partP, qp->gridP, qp->partE, qp->gridE, rho, eta, b->scal);
+  if (int rc = arg_back(b, gx, dgx, n)) return rc;
+  if (int rc = arg_back(b, gs, dgs, n)) return rc;
+  if (int rc = arg_back(b, ys, dys, m)) return rc;
+  if (int rc = eval_end(b, 5, &b->info.last_solve_ms)) return rc;
+  *fx = b->scal_host[0];
+  return FPSQ_OK;
+}
+
+int fpsq_band_qp_hprod(fpsq_band b, fpsq_band_qp qp, const double* v, double sigma, double rho, double eta,
+                       int32_t hessian_approx, double* Hv) {
+  if (!b || !qp || qp->b != b || !v || !Hv) return FPSQ_ERR_ARG;
+  if (hessian_approx != 1 && hessian_approx != 2) {
+    b->err = "band_qp_hprod: hessian_approx must be 1 or 2";
+    return FPSQ_ERR_ARG;
+  }
+  if (int rc = eval_begin(b)) return rc;
+  rho = rho > 0.0 ? rho : 0.0;
+  eta = eta > 0.0 ? eta : 0.0;
+  const size_t n = (size_t)b->n;
+  const double* dv = nullptr;
+  if (int rc = arg_in(b, v, b->in_a, n, &dv)) return rc;
+  double* dHv = arg_out(b, Hv, b->o_p1);
+  bq_launches(b, qp, true, dv, nullptr, sigma, rho, eta, dHv, nullptr, nullptr);
+  if (int rc = arg_back(b, Hv, dHv, n)) return rc;
+  return eval_end(b, 0, &b->info.last_solve_ms);
+}
+
+int fpsq_band_jac_mul(fpsq_band b, int32_t trans, double alpha, const double* x, double beta, double* y) {
+  if (!b || !x || !y || (trans != 0 && trans != 1)) return FPSQ_ERR_ARG;
+  if (!b->have_vals) {
+    b->err = "band_jac_mul: the handle holds no Jacobian values yet (fpsq_band_factorize)";
+    return FPSQ_ERR_STATE;
+  }
+  hipSetDevice(b->device);
+  if (int rc = wait_input(b)) return rc;
+  hipStream_t s = b->stream;
+  const size_t nx = (size_t)(trans ? b->m : b->n), ny = (size_t)(trans ? b->n : b->m);
+  const double* dx = nullptr;
+  if (int rc = arg_in(b, x, trans ? b->in_b : b->in_a, nx, &dx)) return rc;
+  double* dy = arg_out(b, y, trans ? b->o_p1 : b->o_q1);
+  if (dy != y && beta != 0.0) CHK(b, hipMemcpyAsync(dy, y, ny * 8, hipMemcpyDefault, s));
+  const int32_t* perm = b->reordered ? b->rperm : nullptr;
+  const int lg = lane_group(b->nnz, (int64_t)ny);
+  if (trans) {
+    WITH_LANE_GROUP(lg, hipLaunchKernelGGL(k_bq_jacmul<LG>, dim3(bq_grid(b->n, lg)), dim3(256), 0, s, b->t_rowptr, b->t_colind,
+                                           b->t_vals, perm, (const int32_t*)nullptr, alpha, dx, beta, dy, (int)b->n))
+  } else {
+    WITH_LANE_GROUP(lg, hipLaunchKernelGGL(k_bq_jacmul<LG>, dim3(bq_grid(b->m, lg)), dim3(256), 0, s, b->rowptr, b->colind,
+                                           b->vals, (const int32_t*)nullptr, perm, alpha, dx, beta, dy, (int)b->m))
+  }
+  if (int rc = arg_back(b, y, dy, ny)) return rc;
+  CHK(b, hipStreamSynchronize(s));
   return FPSQ_OK;
 }
 }  // extern "C"

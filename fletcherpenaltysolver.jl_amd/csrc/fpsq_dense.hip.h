@@ -1131,4 +1131,237 @@ __global__ __launch_bounds__(256) void k_band_finish(const double* __restrict__ 
   p2[i] = (a1 ? a1[i] : 0.0) - atq[(size_t)i * 2 + 1];
 }
 
+// ---- device-resident equality-QP evaluations on the banded handle (fpsq_band_qp_*): f = 1/2 x' diag(q) x + d'x, c = A x - b.
+// An evaluation is [k_bq_pack] -> k_bq_prologue -> the two sweeps -> k_bq_epilogue [-> k_bq_phi]; A and A' are each read once.
+// Both product kernels give a GROUP of LG lanes (a power of two <= 64, chosen from the mean row length when the model is
+// created) to a row, so that the value / index loads of a row are contiguous across lanes, and walk the row tiles with a
+// grid stride (the grid depends on the shape alone).  Sums are formed in a fixed order -- lanes by xor shuffles, waves in
+// index order, workgroups in index order by k_bq_phi -- so an evaluation is bitwise repeatable; no floating-point atomics.
+
+// sum of v[i] over the 256 threads of the workgroup, in thread 0 (sh: 4 * N doubles); every thread must call it
+template <int N>
+__device__ __forceinline__ void bq_block_sum(double (&v)[N], double* sh) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    for (int o = 32; o > 0; o >>= 1) v[i] += __shfl_xor(v[i], o);
+  if ((threadIdx.x & 63) == 0)
+    for (int i = 0; i < N; ++i) sh[(threadIdx.x >> 6) * N + i] = v[i];
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int i = 0; i < N; ++i) v[i] = ((sh[i] + sh[N + i]) + sh[2 * N + i]) + sh[3 * N + i];
+  __syncthreads();
+}
+
+// the two vectors A multiplies, interleaved: objgrad (HP = false) {g = q x + d, x}; hprod (HP = true) {v, q v}
+template <bool HP>
+__global__ __launch_bounds__(256) void k_bq_pack(const double* __restrict__ x, const double* __restrict__ q,
+                                                 const double* __restrict__ d, double* __restrict__ xg, int n) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double xv = x[j], qv = q[j];
+  f64x2 o;
+  if (HP) o = f64x2{xv, qv * xv};
+  else o = f64x2{qv * xv + d[j], xv};
+  *reinterpret_cast<f64x2*>(xg + (size_t)j * 2) = o;
+}
+
+// One pass over the (stored, i.e. row-permuted) CSR of A with two right-hand sides; row p of the stored order is written
+// where the sweeps read it, r[p] = {A g, -(A x - b)} (objgrad) or {A v, A (q v)} (hprod), zero on the padding, and keep[p] = c
+// resp. A v stays for the epilogue.  GM: the right-hand sides are formed at gather time from x, q, d instead of being read
+// from the packed xg.  Objgrad only: part[2 blk] = this workgroup's slice of f = x.(1/2 q x + d), part[2 blk + 1] = of c.c.
+template <int LG, bool HP, bool GM>
+__global__ __launch_bounds__(256) void k_bq_prologue(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                     const double* __restrict__ vals, const double* __restrict__ xg,
+                                                     const double* __restrict__ x, const double* __restrict__ q,
+                                                     const double* __restrict__ d, const double* __restrict__ bp,
+                                                     double* __restrict__ r, double* __restrict__ keep,
+                                                     double* __restrict__ part, int m, int mpad, int n) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[8];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[2] = {0.0, 0.0};
+  const int ntiles = (mpad + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int p = tile * RPB + g;
+    double a0 = 0.0, a1 = 0.0;
+    if (p < m) {
+      const int e = rowptr[p + 1];
+      for (int k = rowptr[p] + l; k < e; k += LG) {
+        const double a = vals[k];
+        const int c = colind[k];
+        double u0, u1;
+        if (GM) {
+          const double xv = x[c], qv = q[c];
+          u0 = HP ? xv : qv * xv + d[c];
+          u1 = HP ? qv * xv : xv;
+        } else {
+          const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)c * 2);
+          u0 = t.x;
+          u1 = t.y;
+        }
+        a0 += a * u0;
+        a1 += a * u1;
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) {
+      a0 += __shfl_xor(a0, o);
+      a1 += __shfl_xor(a1, o);
+    }
+    if (l == 0 && p < mpad) {  // (a0 = a1 = 0 on the padding rows)
+      double r1 = a1, kv = a0;
+      if (!HP && p < m) {
+        kv = a1 - bp[p];
+        r1 = -kv;
+        red[1] += kv * kv;
+      }
+      *reinterpret_cast<f64x2*>(r + (size_t)p * 2) = f64x2{a0, r1};
+      keep[p] = kv;
+    }
+  }
+  if (!HP) {
+    const int64_t chunk = ((int64_t)n + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
+      const double xv = x[j];
+      red[0] += xv * (0.5 * q[j] * xv + d[j]);
+    }
+    bq_block_sum(red, sh);
+    if (threadIdx.x == 0) {
+      part[(size_t)blockIdx.x * 2] = red[0];
+      part[(size_t)blockIdx.x * 2 + 1] = red[1];
+    }
+  }
+}
+
+// One pass over the CSR of A' (column indices = stored rows of A) on the three vectors the evaluation needs -- q1, q2 (the
+// sweeps' solution y[p] = {q1, q2}, read in the stored order: un-permuted on the fly) and keep (c resp. A v) -- with the row
+// epilogue fused in.  Row j, s1 = (A'q1)_j, s2 = (A'q2)_j, s3 = (A'keep)_j:
+//   objgrad: gs_j = g_j - s1 - sigma s2, p2_j = -s2, grad_j = gs_j + (sigma - q_j) p2_j + rho s3 + eta (x_j - xk_j);
+//            the workgroup also writes its slice of ys = q1 + sigma q2 in the caller's row order (rperm: stored row -> the
+//            caller's, null = identity) and leaves part[2 blk] = its slice of c.ys, part[2 blk + 1] = of |x - xk|^2.
+//   hprod:   Ptv_j = s1, p2_j = q_j v_j - s2, Hv_j = p2_j - q_j Ptv_j + 2 sigma Ptv_j + rho s3 + eta v_j   (out = Hv).
+// out, gs, ys, xk may be null.
+template <int LG, bool HP>
+__global__ __launch_bounds__(256) void k_bq_epilogue(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                     const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                     const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                     const double* __restrict__ x, const double* __restrict__ xk,
+                                                     const double* __restrict__ q, const double* __restrict__ d, double sigma,
+                                                     double rho, double eta, double* __restrict__ out,
+                                                     double* __restrict__ gs, double* __restrict__ ys,
+                                                     double* __restrict__ part, int n, int m) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[8];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[2] = {0.0, 0.0};
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (j < n) {
+      const int e = t_rowptr[j + 1];
+      for (int k = t_rowptr[j] + l; k < e; k += LG) {
+        const double a = t_vals[k];
+        const int p = t_colind[k];
+        const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * 2);
+        s1 += a * t.x;
+        s2 += a * t.y;
+        s3 += a * keep[p];
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) {
+      s1 += __shfl_xor(s1, o);
+      s2 += __shfl_xor(s2, o);
+      s3 += __shfl_xor(s3, o);
+    }
+    if (l == 0 && j < n) {
+      const double xv = x[j], qv = q[j];
+      if (HP) {
+        out[j] = (qv * xv - s2) - qv * s1 + 2.0 * sigma * s1 + rho * s3 + eta * xv;
+      } else {
+        const double gsv = (qv * xv + d[j]) - s1 - sigma * s2, p2 = -s2;
+        const double dx = eta > 0.0 ? xv - (xk ? xk[j] : 0.0) : 0.0;
+        if (gs) gs[j] = gsv;
+        if (out) out[j] = gsv + (sigma - qv) * p2 + rho * s3 + eta * dx;
+        red[1] += dx * dx;
+      }
+    }
+  }
+  if (!HP) {
+    const int64_t chunk = ((int64_t)m + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < m ? lo + chunk : m;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+      const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * 2);
+      const double yv = t.x + sigma * t.y;
+      if (ys) ys[rperm ? rperm[p] : p] = yv;
+      red[0] += keep[p] * yv;
+    }
+    bq_block_sum(red, sh);
+    if (threadIdx.x == 0) {
+      part[(size_t)blockIdx.x * 2] = red[0];
+      part[(size_t)blockIdx.x * 2 + 1] = red[1];
+    }
+  }
+}
+
+// The scalars of an objgrad from the workgroups' partials, each summed in index order (one workgroup: thread t takes a
+// contiguous run, then the fixed tree of bq_block_sum): out = {phi, f, c.c, c.ys, |x - xk|^2},
+// phi = f - c.ys + rho/2 c.c + eta/2 |x - xk|^2.
+__global__ __launch_bounds__(256) void k_bq_phi(const double* __restrict__ partP, int nP, const double* __restrict__ partE,
+                                                int nE, double rho, double eta, double* __restrict__ out) {
+  __shared__ double sh[16];
+  double red[4] = {0.0, 0.0, 0.0, 0.0};
+  const int cp = (nP + 255) / 256, ce = (nE + 255) / 256;
+  for (int i = threadIdx.x * cp; i < min(nP, ((int)threadIdx.x + 1) * cp); ++i) {
+    red[0] += partP[(size_t)i * 2];
+    red[1] += partP[(size_t)i * 2 + 1];
+  }
+  for (int i = threadIdx.x * ce; i < min(nE, ((int)threadIdx.x + 1) * ce); ++i) {
+    red[2] += partE[(size_t)i * 2];
+    red[3] += partE[(size_t)i * 2 + 1];
+  }
+  bq_block_sum(red, sh);
+  if (threadIdx.x == 0) {
+    double phi = red[0] - red[2];
+    phi += 0.5 * rho * red[1];
+    phi += 0.5 * eta * red[3];
+    out[0] = phi;
+    out[1] = red[0];
+    out[2] = red[1];
+    out[3] = red[2];
+    out[4] = red[3];
+  }
+}
+
+// y[o(r)] = alpha sum_k vals[k] x[i(colind[k])] + beta y[o(r)] over the rows of a CSR matrix, a lane group per row;
+// in_perm / out_perm (null = identity) translate stored rows of A to the caller's: A x takes out_perm, A' x takes in_perm
+template <int LG>
+__global__ __launch_bounds__(256) void k_bq_jacmul(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                   const double* __restrict__ vals, const int32_t* __restrict__ in_perm,
+                                                   const int32_t* __restrict__ out_perm, double alpha,
+                                                   const double* __restrict__ x, double beta, double* y, int rows) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (rows + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int r = tile * RPB + g;
+    double s = 0.0;
+    if (r < rows) {
+      const int e = rowptr[r + 1];
+      for (int k = rowptr[r] + l; k < e; k += LG) {
+        const int c = colind[k];
+        s += vals[k] * x[in_perm ? in_perm[c] : c];
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (l == 0 && r < rows) {
+      const int o = out_perm ? out_perm[r] : r;
+      y[o] = alpha * s + (beta != 0.0 ? beta * y[o] : 0.0);
+    }
+  }
+}
+
 }  // namespace fpsq

@@ -34,6 +34,7 @@ class DeviceEqQP:
         for k, v in opt_overrides.items():
             setattr(opts, k, v)
         self.opts = opts
+        self.device = int(opts.device)
         h = C.c_void_p()
         if self._lib.fpsq_create(C.byref(h), qp.n, qp.m, C.byref(opts)) != 0:
             raise FpsqError(self._lib.fpsq_last_error(None).decode())
@@ -155,6 +156,126 @@ class DeviceEqQP:
         if getattr(self, "_h", None):
             self._lib.fpsq_qp_destroy(self._q)
             self._lib.fpsq_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBandEqQP:
+    """The same device-resident eq-QP model on the DIRECT back-end: the block-banded factorisation of M = A A' + delta I
+    (`fpsq_band_*`, the device counterpart of the reference's default `qds_solver = :ldlt`) with `fpsq_band_qp_objgrad` /
+    `fpsq_band_qp_hprod` on the CACHED factor.  The factor is rebuilt lazily -- once, at the next evaluation -- after
+    `set_delta` or `set_jacobian_values`; `info()["factorizations"]` counts how many this object has run.
+    ldlt_tol / ldlt_r2: the dynamic regularisation of `LDLtSolver`, defaults as in qdsolver._DirectQDSolver (sqrt(eps),
+    -sqrt(eps); "drop" drops a vanishing pivot).  Has the surface `fps_solve_device` uses on DeviceEqQP."""
+
+    def __init__(self, qp, sigma=1e3, rho=1.0, delta=0.0, eta=0.0, device=0, ldlt_tol=None, ldlt_r2=None):
+        from .qdsolver import _ldlt_r2
+
+        self._lib = _lib.load()
+        self.qp, self.sigma, self.rho, self.delta, self.eta = qp, sigma, rho, float(delta), eta
+        self.device = int(device)
+        self._h = self._q = None
+        rp = np.ascontiguousarray(qp.rowptr, dtype=np.int32)
+        ci = np.ascontiguousarray(qp.colind, dtype=np.int32)
+        h = C.c_void_p()
+        if self._lib.fpsq_band_create(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, self.device) != 0:
+            raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
+        self._h = h
+        try:
+            se = float(np.sqrt(np.finfo(float).eps))
+            self.ldlt_tol = se if ldlt_tol is None else float(ldlt_tol)
+            self.ldlt_r2 = _ldlt_r2(ldlt_r2)
+            self._check(self._lib.fpsq_band_set_regularization(h, self.ldlt_tol, -self.ldlt_r2))
+            q = C.c_void_p()
+            self._check(self._lib.fpsq_band_qp_create(h, np.ascontiguousarray(qp.qdiag).ctypes.data,
+                                                      np.ascontiguousarray(qp.d).ctypes.data,
+                                                      np.ascontiguousarray(qp.b).ctypes.data, C.byref(q)))
+            self._q = q
+        except Exception:
+            self.close()
+            raise
+        self._vals = np.ascontiguousarray(qp.vals, dtype=np.float64)   # CSR-order values the next factorisation takes
+        self._stale, self._fact_rc, self.factorizations = True, 0, 0
+        self._in_stream = -1
+
+    def _check(self, rc):
+        if rc < 0:
+            raise FpsqError(self._lib.fpsq_band_last_error(self._h).decode())
+        return rc
+
+    def _order(self, *args):
+        """Device tensors among the arguments are produced on torch's current stream: register it, so that the handle's
+        stream waits for it at the start of every call (fpsq_band_set_input_stream).  No host synchronisation."""
+        st = _lib.producer_stream(*args)
+        if st is not None and st != self._in_stream:
+            self._check(self._lib.fpsq_band_set_input_stream(self._h, 1, st))
+            self._in_stream = st
+
+    def set_delta(self, delta):
+        if float(delta) != self.delta:
+            self._stale = True
+        self.delta = float(delta)
+
+    def set_jacobian_values(self, vals):
+        """`jac_coord!` output at a new x in CSR order (numpy array, torch tensor on the host or the device, or a raw address);
+        the factor is stale from here on and is rebuilt at the next evaluation.  The values are read THEN: keep them unchanged."""
+        self._vals = vals
+        self._stale = True
+
+    def _factor(self):
+        """The lazy (re-)factorisation; returns its soft code (1: M not positive definite and no regularisation)."""
+        if self._stale:
+            self._order(self._vals)
+            self._fact_rc = self._check(self._lib.fpsq_band_factorize(self._h, _lib.ptr(self._vals), self.delta, None))
+            self.factorizations += 1
+            self._stale = False
+        if self._fact_rc:
+            import warnings
+            warnings.warn("DeviceBandEqQP: A A' + delta I is not positive definite (no valid factorisation)")
+        return self._fact_rc
+
+    def objgrad(self, x, gx=None, ys=None, gs=None, xk=None):
+        """x / gx / ys / gs / xk: numpy arrays, torch tensors (host or device) or raw addresses.  Returns (fx, rc); with
+        rc = 1 (failed factorisation) nothing was evaluated: fx is nan and the outputs are untouched."""
+        if self._factor():
+            return float("nan"), self._fact_rc
+        fx = C.c_double()
+        self._order(x, gx, ys, gs, xk)
+        self._check(self._lib.fpsq_band_qp_objgrad(self._h, self._q, _lib.ptr(x), self.sigma, self.rho, self.eta,
+                                                   _lib.ptr(xk), C.byref(fx), _lib.ptr(gx), _lib.ptr(ys), _lib.ptr(gs)))
+        return fx.value, 0
+
+    def hprod(self, v, Hv, hessian_approx=2):
+        """hprod!(::FletcherPenaltyNLP, x, v, Hv) on the device (include/fpsq.h fpsq_band_qp_hprod).  Returns rc."""
+        if self._factor():
+            return self._fact_rc
+        self._order(v, Hv)
+        return self._check(self._lib.fpsq_band_qp_hprod(self._h, self._q, _lib.ptr(v), self.sigma, self.rho, self.eta,
+                                                        int(hessian_approx), _lib.ptr(Hv)))
+
+    def jac_mul(self, trans, alpha, x, beta, y):
+        """y = alpha op(A) x + beta y with the model's Jacobian (fpsq_band_jac_mul; trans = 0: A, 1: A')."""
+        self._factor()   # (the values reach the handle with a factorisation)
+        self._order(x, y)
+        return self._check(self._lib.fpsq_band_jac_mul(self._h, int(trans), float(alpha), _lib.ptr(x), float(beta),
+                                                       _lib.ptr(y)))
+
+    def info(self):
+        i = _lib.BandInfo()
+        self._check(self._lib.fpsq_band_get_info(self._h, C.byref(i)))
+        return {**i.as_dict(), "factorizations": self.factorizations}
+
+    def close(self):
+        if getattr(self, "_q", None):
+            self._lib.fpsq_band_qp_destroy(self._q)
+            self._q = None
+        if getattr(self, "_h", None):
+            self._lib.fpsq_band_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -613,12 +613,12 @@ def _update_parameters(pen, meta, feas):
 # ------------------------------------------------------------------ the same loop on the device-resident eq-QP model
 
 class _DevicePenalty:
-    """The penalty function of a DeviceEqQP (fpsq_qp_objgrad / fpsq_qp_hprod): every vector stays in HBM (torch
-    tensors); the host only sees scalars."""
+    """The penalty function of a DeviceEqQP (fpsq_qp_objgrad / fpsq_qp_hprod) or a DeviceBandEqQP (fpsq_band_qp_*): every
+    vector stays in HBM (torch tensors); the host only sees scalars."""
 
     def __init__(self, dev, torch, hessian_approx=2):
         self.dev, self.torch, self.hessian_approx = dev, torch, int(hessian_approx)
-        d = torch.device("cuda", int(dev.opts.device))
+        d = torch.device("cuda", int(dev.device))
         qp = dev.qp
         self.q = torch.from_numpy(np.ascontiguousarray(qp.qdiag)).to(d)
         self.d = torch.from_numpy(np.ascontiguousarray(qp.d)).to(d)
@@ -676,8 +676,9 @@ class _DevicePenalty:
 
 
 def fps_solve_device(dev, x0, *, atol=_SE, rtol=_SE, max_iter=100, max_time=300.0, verbose=0, **kwargs):
-    """fps_solve on a device-resident equality QP (`DeviceEqQP`): x0 and every iterate are torch tensors in HBM, each
-    obj/grad! is one fpsq_qp_objgrad, each Hessian product of the `trunk` sub-solver one fpsq_qp_hprod.
+    """fps_solve on a device-resident equality QP (`DeviceEqQP`: the iterative back-end, or `DeviceBandEqQP`: the banded
+    direct one): x0 and every iterate are torch tensors in HBM, each obj/grad! is one fpsq_qp_objgrad /
+    fpsq_band_qp_objgrad, each Hessian product of the `trunk` sub-solver one fpsq_qp_hprod / fpsq_band_qp_hprod.
     Returns ExecutionStats whose `solution` / `multipliers` are device tensors."""
     import torch
 

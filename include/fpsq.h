@@ -374,6 +374,41 @@ int fpsq_band_solve_two_least_squares(fpsq_band b, const double *rhs1, const dou
                                       double *p2, double *q2);
 int fpsq_band_get_info(fpsq_band b, fpsq_band_info *info);
 
+/* ---- the device-resident equality-QP user model on the banded handle: the fpsq_qp_* group of the iterative handle on the
+ * DIRECT back-end.   f(x) = 1/2 x' diag(q) x + d'x,   c(x) = A x - b,   A = the Jacobian the handle was last factorised with.
+ * These entries use the CACHED factor: the caller factorises (fpsq_band_factorize[_coo]) when the Jacobian's values or delta
+ * change -- the counterpart of fpsq_set_jacobian_values on the iterative handle -- and an evaluation costs no
+ * factorisation.  Without a valid factor they return FPSQ_ERR_STATE like the solve entries.  Vectors are host or device
+ * pointers; device-resident ones are read and written in place (no staging copy), and an evaluation then moves nothing
+ * between host and device but its scalars, once.  Row permutation, padding and the two elimination chains stay internal.
+ *   fpsq_band_qp_objgrad  one `objgrad!(::FletcherPenaltyNLP, x, gx)` (src/model-Fletcherpenaltynlp.jl:403-437) on this model
+ *                         (the constraint Hessians vanish: Sstw = 0, Hsv = q .* v):  (p1, q1, p2, q2) = solve_two_mixed(g, c),
+ *                         ys = q1 + sigma q2, gs = p1 + sigma p2, gx = gs + (sigma - q) .* p2 + rho A'c + eta (x - xk),
+ *                         *fx = f - c'ys + rho/2 c'c + eta/2 |x - xk|^2 (a HOST double).  gx, ys, gs may be NULL; xk NULL
+ *                         with eta > 0 means xk = 0.  The rho / eta terms are added when the parameter is positive.
+ *                         Sums are formed in a fixed order: two calls with the same arguments return the same bits.
+ *   fpsq_band_qp_hprod    one `hprod!` with hessian_approx = 2 (:521-570): (p1, _, p2, _) = solve_two_least_squares(v, q .* v),
+ *                         Ptv = v - p1, Hv = p2 - q .* Ptv + 2 sigma Ptv + rho A'(A v) + eta v.  hessian_approx = 1 (:572-634)
+ *                         returns the SAME vector and launches nothing more: its extra terms vanish identically on this model
+ *                         (Ssv = ghjvprod = 0 for linear constraints, the exact solve of a zero right-hand side is zero, and
+ *                         hprod with obj_weight = 0 is zero).  Any other value: FPSQ_ERR_ARG.
+ *   fpsq_band_jac_mul     y = alpha op(A) x + beta y, trans = 0: A (x: n, y: m), 1: A' (x: m, y: n), in the caller's row order.
+ *   fpsq_band_set_input_stream  as fpsq_set_input_stream ("INPUT READINESS" above): once a stream is registered (enabled != 0;
+ *                         NULL = the legacy default stream), each of the calls above and fpsq_band_factorize[_coo] first makes
+ *                         the handle's stream wait (event, no host block) for everything enqueued on that stream so far.
+ *                         Outputs are complete when a call returns, so there is no output-ordering switch.
+ * Destroy a model before the handle it was created on.  FPSQ_BAND_QP_G=1 (read by fpsq_band_qp_create; A/B runs) forms g at
+ * gather time in the A product instead of writing it first. */
+typedef struct fpsq_band_qp_s *fpsq_band_qp;
+int fpsq_band_qp_create(fpsq_band b, const double *qdiag, const double *d, const double *bvec, fpsq_band_qp *out);
+int fpsq_band_qp_destroy(fpsq_band_qp qp);
+int fpsq_band_qp_objgrad(fpsq_band b, fpsq_band_qp qp, const double *x, double sigma, double rho, double eta,
+                         const double *xk, double *fx, double *gx, double *ys, double *gs);
+int fpsq_band_qp_hprod(fpsq_band b, fpsq_band_qp qp, const double *v, double sigma, double rho, double eta,
+                       int32_t hessian_approx, double *Hv);
+int fpsq_band_jac_mul(fpsq_band b, int32_t trans, double alpha, const double *x, double beta, double *y);
+int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
+
 /* ---- introspection for benchmarks / profiling */
 typedef struct {
   int64_t n, m, nnz;
