@@ -860,6 +860,9 @@ struct fpsq_solver_s {
   LaneCtl* ctl_raw;             // constant {ca = 1, cb = 0, done = 0}: raw partial products before an all-reduce
   LaneCtl* ctl_pm;              // constant {1, -1}
   LaneCtl* ctl_mp;              // constant {-1, 1}
+  LaneCtl* ctl_m0;              // constant {-1, 0}: p2 = -A'q2 (two_mixed_device)
+  bool craig_x = false;         // FPSQ_CRAIG_X=1: CRAIG carries x through its loop (the recurrence xs += e0 v~) instead of p2 = xsign A'q2 behind it
+  bool craig_v_alone = false;   // FPSQ_CRAIG_X=2 (tests): no recurrence, and p2 ALWAYS by the single-lane product k_spmv<1, ..>, never inside a tail launch
   Comm* comm = nullptr;         // null: single GPU
   // Halo mode of the sharded handle (fpsq_comm_set_halo): n is the length of this rank's COLUMN WINDOW; its first
   // `ovl` entries are shared with rank - 1, its last `ovr` with rank + 1; sums over n-vectors run over the owned prefix
@@ -1838,12 +1841,19 @@ inline bool single_gpu_tail(fpsq_handle h) {
 // The tail's raw A' product on one GPU: its rows go straight into the call's result (k_spmv<.., GRAD>; grad(phi): two lanes,
 // Hv: one).  False: the layout has no GRAD variant, nothing was launched (the caller launches the product and the kernel that
 // combines its rows).
-template <int NL>
+// VRAW (two lanes, FPSQ_FUSE_TAIL=0): the rows ARE written, as launch_spmv<2> writes them, and v = ge.vsign A'ge.y2 goes to ge.vout
+// beside them (nothing else of `ge` is used).
+template <int NL, bool VRAW = false>
 bool launch_at_tail(fpsq_handle h, const double* x, double* yout, const GradEpi& ge, Gates gates = {}) {
   const DevCsr& M = h->AT;
   if (!M.sorted) return false;
   const int per_xcd = (M.nblk + 7) / 8;
   const HaloRows hr{h->ovl, h->n - h->ovr, h->halo_raw};
+  if constexpr (VRAW)
+    launch_product(h, k_spmv<NL, TAG_AT, true, true, false, true, false, true>, dim3(per_xcd * 8), M.view(),
+                   x, (const double*)nullptr, yout, h->ctl_raw, h->ctl_raw, (double*)nullptr, per_xcd,
+                   seg_none(), seg_none(), gates.c0, gates.c1, h->strT, hr, ge);
+  else
   launch_product(h, k_spmv<NL, TAG_AT, true, true, false, true, true>, dim3(per_xcd * 8 + (ge.fx.out != nullptr ? 1 : 0)), M.view(),
                  x, (const double*)nullptr, yout, h->ctl_raw, h->ctl_raw, (double*)nullptr, per_xcd,
                  seg_none(), seg_none(), gates.c0, gates.c1, h->strT, hr, ge);
@@ -1867,6 +1877,7 @@ const LaneCtl* const_ctl(fpsq_handle h, double ca, double cb) {
   if (ca == 1.0 && cb == 0.0) return h->ctl_raw;
   if (ca == 1.0 && cb == -1.0) return h->ctl_pm;
   if (ca == -1.0 && cb == 1.0) return h->ctl_mp;
+  if (ca == -1.0 && cb == 0.0) return h->ctl_m0;
   hipLaunchKernelGGL(k_set_ctl, dim3(1), dim3(1), 0, h->stream, h->ctl_tmp, ca, cb);
   h->launches++;
   return h->ctl_tmp;
@@ -2186,7 +2197,8 @@ struct Lane {
   double lambda = 0.0;          // LSQR regularisation; MINRES: shift of A A' + lambda I
   double delta = 0.0;           // CRAIG: M = (1/delta) I, sqd when != 0
   double xsign = 1.0;           // CRAIG: xs accumulates xsign * x
-  double* x = nullptr;          // LSQR, MINRES: solution (m).  CRAIG: xs (n)
+  double* x = nullptr;          // LSQR, MINRES: solution (m).  CRAIG: xs (n); null: x is not carried through the loop -- the
+                                //   caller forms xs = xsign A'y from the final y (two_mixed_device)
   double* y = nullptr;          // CRAIG: y (m)
   fpsq_stats* st = nullptr;     // destination of the final stats: an element of the host-mapped h->hstats
   fpsq_stats* st_dev = nullptr; // its device alias (filled by run_krylov / run_minres)
@@ -2657,7 +2669,8 @@ struct KrylovRun {
     u.a = L.x;
     u.b = h->Cw2;
     u.len = n;
-    lng = u;
+    // CRAIG without x in the loop (Lane::x null): nothing long rides -- w2 only ever feeds x
+    lng = L.kind == LANE_CRAIG && L.x == nullptr ? seg_none() : u;
     UpdSeg v{};
     v.kind = L.kind == LANE_LNLQ ? UPD_LNLQ_SHORT : UPD_CRAIG_SHORT;
     v.it = (int)it;
@@ -2771,17 +2784,20 @@ struct KrylovRun {
         g.len = m;
         g.sum_len = m;
         g.nblk = gm;
-        z.p[0] = L.x;
-        z.n[0] = n;
         z.p[1] = L.y;
         z.n[1] = m;
         z.p[2] = h->Cw;
         z.n[2] = m;
-        if (L.delta != 0.0) {
-          z.p[3] = h->Cw2;
-          z.n[3] = n;
+        nzblk = gm;
+        if (L.x != nullptr) {  // (the long recurrence: x, and w2 when regularised)
+          z.p[0] = L.x;
+          z.n[0] = n;
+          if (L.delta != 0.0) {
+            z.p[3] = h->Cw2;
+            z.n[3] = n;
+          }
+          nzblk = gn;
         }
-        nzblk = gn;
       }
     }
     ht_mark(h, 3);
@@ -3756,12 +3772,21 @@ int minres_k_device(fpsq_handle h, const double* bp0, const double* bq0, const d
   return 0;
 }
 
+// CRAIG without x in its loop (one GPU; FPSQ_CRAIG_X=1: keep the recurrence; LNLQ keeps it: its x is not A'y at the LQ point; sharded
+// handles keep it): see two_mixed_device
+constexpr double kMixedXSign = -1.0;  // solve_two_mixed hands out p2 = -x of the least-norm solve (src/solve_linear_system.jl:132-133)
+inline bool craig_x_from_y(fpsq_handle h) {
+  return h->opt.kkt_method != FPSQ_KKT_MINRES_K && h->opt.ln_method != FPSQ_LN_LNLQ && !h->comm && !h->craig_x;
+}
+
 // device-side solve_two_mixed: g (n), c (m) device pointers; results left in h->p1, h->Lx[0] (q1), h->Cx (p2), h->Cy (q2)
 // defer_p1: the caller forms p1 = g - A'q1 itself (qp_objgrad pairs that product with A'c in one two-RHS launch)
+// defer_p2 (only where craig_x_from_y): the caller's tail forms p2 = -A'q2 itself, in the same launch (GradEpi::y2)
 // affine_shift != null (fast start): c is NOT formed yet; CRAIG's right-hand side -(A z - shift), z in the long pair's
 // CRAIG lane, comes out of the LSQR start-up product and A z - shift is left in `c` (see run_krylov)
 int two_mixed_device(fpsq_handle h, const double* g, double* c, bool defer_p1 = false,
-                     const double* affine_shift = nullptr, const TailFn* tail = nullptr, const RunRequest& req = {}) {
+                     const double* affine_shift = nullptr, const TailFn* tail = nullptr, const RunRequest& req = {},
+                     bool defer_p2 = false) {
   if (h->opt.kkt_method == FPSQ_KKT_MINRES_K) {
     if (defer_p1 || affine_shift || tail) {
       h->err = "kkt_method = MINRES_K serves fpsq_solve_two_mixed / fpsq_solve_two_least_squares / fpsq_ys_gs only";
@@ -3787,12 +3812,22 @@ int two_mixed_device(fpsq_handle h, const double* g, double* c, bool defer_p1 = 
     lanes[1].affine_out = c;
   }
   lanes[1].delta = h->delta;
-  lanes[1].xsign = -1.0;
-  lanes[1].x = h->Cx;
+  lanes[1].xsign = kMixedXSign;
+  // One GPU: CRAIG does not carry x through its loop.  Every CRAIG iterate satisfies x_k = A'y_k (first block row of
+  // [-I A'; A delta I][x; y] = [0; b], with or without the regularisation), nothing in the loop reads x -- the stopping tests use
+  // the scalar ||x||^2 -- and the recurrence costs 3 passes over n per iteration (5 with w2, delta != 0) that ride in the A
+  // product.  p2 = xsign A'q2 is formed ONCE, behind the loop and under the tail's gates, from the final y: by the same one-lane
+  // product (k_spmv<1, ..>) -- or, at the end of an evaluation, inside the launch of the tail's two-lane product A'[q1, c], whose
+  // workgroups sum the rows of A'q2 the way that kernel does (GradEpi::y2, defer_p2) -- so that p2 / v is bitwise the same
+  // whichever entry point or tail variant asks for it.
+  const bool x_from_y = craig_x_from_y(h);
+  lanes[1].x = x_from_y ? nullptr : h->Cx;
   lanes[1].y = h->Cy;
   lanes[1].st = &h->hstats[1];
   // p1 = rhs1 - Aop' q1                                                   :126-127
   TailFn full = [&](const TailCtx& t) -> int {
+    if (x_from_y && !defer_p2)
+      if (int rc = at_product_const(h, lanes[1].xsign, h->Cy, 0.0, nullptr, h->Cx, t.gates)) return rc;
     if (!defer_p1)
       if (int rc = at_product_const(h, -1.0, h->Lx[0], 1.0, g, h->p1, t.gates)) return rc;
     return tail ? (*tail)(t) : 0;
@@ -3962,6 +3997,10 @@ int fpsq_create(fpsq_handle* out, int64_t n, int64_t m, const fpsq_options* opts
     if (const char* at = std::getenv("FPSQ_FUSE_PROBE_AT")) h->fuse_probe_at = std::atoll(at);
   }
   if (const char* ev = std::getenv("FPSQ_FUSE_TAIL")) h->fuse_tail = std::atoi(ev) != 0;
+  if (const char* ev = std::getenv("FPSQ_CRAIG_X")) {
+    h->craig_x = std::atoi(ev) == 1;
+    h->craig_v_alone = std::atoi(ev) == 2;
+  }
   if (const char* ev = std::getenv("FPSQ_ADOPT_STREAM")) h->adopt_streams = std::atoi(ev) != 0;
   if (const char* ev = std::getenv("FPSQ_DEBUG_RIDE_BREAK")) h->ride_break = std::atoi(ev) != 0;
   if (const char* ev = std::getenv("FPSQ_DEBUG_RIDE_DELAY")) h->ride_delay = std::atoi(ev);
@@ -3998,7 +4037,7 @@ int fpsq_create(fpsq_handle* out, int64_t n, int64_t m, const fpsq_options* opts
   hipEventCreate(&h->ev1);
   void* p = nullptr;
   const size_t state_bytes = sizeof(LsqrState) * 6 + sizeof(CraigState) * 3 + sizeof(MinresState) * 2 + sizeof(LnlqState) * 3 +
-                             4 * sizeof(LaneCtl) + 64 * sizeof(double);
+                             5 * sizeof(LaneCtl) + 64 * sizeof(double);
   if ((e = hipMalloc(&p, state_bytes)) != hipSuccess) return fail("hipMalloc", e);
   h->allocs.push_back(p);
   hipMemset(p, 0, state_bytes);
@@ -4044,6 +4083,8 @@ int fpsq_create(fpsq_handle* out, int64_t n, int64_t m, const fpsq_options* opts
   cp += sizeof(LaneCtl);
   h->ctl_mp = (LaneCtl*)cp;
   cp += sizeof(LaneCtl);
+  h->ctl_m0 = (LaneCtl*)cp;
+  cp += sizeof(LaneCtl);
   h->dscal = (double*)cp;
   h->comm_scal = h->dscal + 32;
   {
@@ -4058,6 +4099,9 @@ int fpsq_create(fpsq_handle* out, int64_t n, int64_t m, const fpsq_options* opts
     raw.ca = -1.0;
     raw.cb = 1.0;
     hipMemcpy(h->ctl_mp, &raw, sizeof raw, hipMemcpyHostToDevice);
+    raw.ca = -1.0;
+    raw.cb = 0.0;
+    hipMemcpy(h->ctl_m0, &raw, sizeof raw, hipMemcpyHostToDevice);
   }
   hipDeviceSynchronize();
   *out = h;
@@ -4562,6 +4606,9 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
   // the epilogue then starts with k_ys, which also applies the final LSQR x update (no launch of its own for it)
   req.absorb_flush = paired && fast && !(h->ab_mask & 2);
   const double seq = (h->call_seq += 1.0);
+  // CRAIG without x in its loop: the one-launch tail forms v = p2 = -A'q2 on the side (else two_mixed_device does, ahead of the tail)
+  // (FPSQ_FUSE_TAIL=0 too: there the plain raw product carries the same single-lane pass -- k_spmv<2, .., VRAW>)
+  const bool v_in_tail = paired && craig_x_from_y(h) && h->AT.sorted && h->AT.padded && !h->craig_v_alone;
   // everything behind the two solves: enqueued speculatively (gated on the recurrences' `done` flags) by run_krylov when
   // the iteration count of the previous evaluation is known, else here
   TailFn epi = [&](const TailCtx& t) -> int {
@@ -4610,6 +4657,11 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
         GradEpi ge{};
         ge.g = h->g;
         ge.v = h->Cx;
+        if (v_in_tail) {  // (v = p2 = kMixedXSign A'q2 is formed in this launch, from the final q2)
+          ge.y2 = h->Cy;
+          ge.vsign = kMixedXSign;
+          ge.vout = h->Cx;
+        }
         ge.q = qp->q;
         ge.x = dx;
         ge.xk = dxk;
@@ -4621,9 +4673,17 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
         ge.fx = grad_fx ? fa : none;
         one_launch = launch_at_tail<2>(h, h->SP, h->LP, ge, t.gates);
       }
-      if (!one_launch) {  // (the product writes its rows as ever: combine them in a launch of their own)
+      if (!one_launch && v_in_tail) {  // (FPSQ_FUSE_TAIL=0: the plain raw product, with v on the side: k_spmv<2, .., VRAW>)
+        GradEpi ge{};
+        ge.y2 = h->Cy;
+        ge.vsign = kMixedXSign;
+        ge.vout = h->Cx;
+        launch_at_tail<2, true>(h, h->SP, h->LP, ge, t.gates);
+      } else if (!one_launch) {
         launch_spmv<2>(h, TAG_AT, h->SP, nullptr, h->LP, h->ctl_raw, h->ctl_raw, nullptr, seg_none(), seg_none(), h->halo, nullptr,
                        t.gates);
+      }
+      if (!one_launch) {  // (the product writes its rows as ever: combine them in a launch of their own)
         if (h->halo)
           if (int rc = halo_finish<2>(h, nullptr, h->LP, h->ctl_raw, h->ctl_raw, nullptr, t.gates)) return rc;
         hipLaunchKernelGGL(k_qp_penalty_grad, dim3(grad_fx ? gn + 1 : gn), dim3(kBlock), 0, s, (const double*)nullptr, h->g, h->LP,
@@ -4679,7 +4739,7 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
     }
     return 0;
   };
-  if (int rc = two_mixed_device(h, h->g, h->c, paired, fast ? qp->b : nullptr, local_vec ? &epi : nullptr, req)) return rc;
+  if (int rc = two_mixed_device(h, h->g, h->c, paired, fast ? qp->b : nullptr, local_vec ? &epi : nullptr, req, v_in_tail)) return rc;
   if (!local_vec)
     if (int rc = epi(TailCtx{})) return rc;
   if (gx && dgx != gx) HIPCHK(h, hipMemcpyAsync(gx, h->gx, nb, hipMemcpyDefault, s));

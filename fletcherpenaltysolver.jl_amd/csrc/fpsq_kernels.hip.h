@@ -1133,6 +1133,12 @@ struct GradEpi {
   const double *p1, *p2;
   double sigma, rho, eta;
   double *gs, *gx, *hv;
+  // two lanes, CRAIG without x in its loop (two_mixed_device): v is not loaded -- row i of v = vsign A'y2 is summed by the same
+  // workgroup from the same matrix entries (a single-lane pass through the product buffer ahead of the two-lane one: the sum
+  // of k_spmv<1, ..>, bit for bit) and stored to vout, where hprod! and the callers of the two-launch tail find it.  null: v is loaded
+  const double* y2;
+  double vsign;
+  double* vout;
   FxArgs fx;  // fx.out != null: workgroup 0 of the grid reduces the evaluation's partial sums to phi (k_qp_penalty_grad's last one does)
 };
 

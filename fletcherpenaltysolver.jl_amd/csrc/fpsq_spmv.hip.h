@@ -169,14 +169,24 @@ __device__ __forceinline__ void csort_fetch(const CsrView& A, int L, int cbase, 
 // GRAD (the tail of an evaluation on one GPU: NL = 2, the raw product A'[q1, c], round 5): the rows are not written -- each goes
 // straight into the gradient row it is needed for (qp_grad_row: gs and gx), which saves writing and re-reading the 16 MB product and
 // the launch of k_qp_penalty_grad; the FIRST workgroup of the grid reduces phi (that kernel's last one did).  Bitwise the two-kernel tail
-// (FPSQ_FUSE_TAIL=0).
-template <int NL, int TAG, bool IDX16 = false, bool PAD = false, bool HALO = false, bool CSORT = false, bool GRAD = false>
+// (FPSQ_FUSE_TAIL=0).  With GradEpi::y2 the third product of the tail, v = vsign A'y2, shares the launch: the block's entries are
+// in registers anyway, so the workgroup gathers y2 for them as well, parks those products in the (single-lane) head of the product
+// buffer, sums its rows exactly as k_spmv<1, ..> does, and only then stages the two-lane products -- 0.8 MB of gathers and one more
+// trip through LDS instead of another stream of the matrix; the buffer stays at 32 KB (three lanes side by side: 48 KB, three
+// workgroups per CU instead of four).
+// VRAW (FPSQ_FUSE_TAIL=0 on such a handle: NL = 2, not GRAD): the plain raw product -- rows written by row_epilogue as ever, for
+// k_qp_penalty_grad -- with the same single-lane pass for v ahead of it, so that the two-launch tail stays two launches.  A template
+// parameter: the one-launch tail's kernel carries none of it.
+template <int NL, int TAG, bool IDX16 = false, bool PAD = false, bool HALO = false, bool CSORT = false, bool GRAD = false,
+          bool VRAW = false>
 __global__ __launch_bounds__(kBlock) void k_spmv(CsrView A, const double* __restrict__ x, const double* yin,
                                                  double* yout, const LaneCtl* ctl0, const LaneCtl* ctl1,
                                                  double* partials, int blk_per_xcd, const UpdSeg u0, const UpdSeg u1,
                                                  const LaneCtl* gate0, const LaneCtl* gate1, int pstride,
                                                  const HaloRows hr, const GradEpi ge) {
   static_assert(!GRAD || (TAG == 1 && !HALO && PAD), "the result epilogues: raw A' products of one GPU, padded blocks");
+  static_assert(!VRAW || (NL == 2 && !GRAD && TAG == 1 && !HALO && PAD), "v beside the raw rows: the two-lane A' product of one GPU");
+  constexpr bool VPASS = NL == 2 && (GRAD || VRAW);  // the single-lane pass for v = vsign A'y2 may run (GRAD: when ge.y2 is set)
   // exactly 32 KB of LDS for two right-hand sides (FOUR workgroups per CU -- measured, tools/stream_probe.hip: 30 KB would
   // admit five, 24 KB six; tiles of 1536 entries were slower all the same): the reduction scratch
   // aliases the head of the product buffer
@@ -293,11 +303,15 @@ __global__ __launch_bounds__(kBlock) void k_spmv(CsrView A, const double* __rest
     [[maybe_unused]] double gpre[4] = {0.0, 0.0, 0.0, 0.0};  // GRAD: the epilogue's operands of the first row pass, requested here like yin
     if constexpr (GRAD) {
       gpre[0] = NL == 2 ? ge.g[r0 + rq0] : ge.p1[r0 + rq0];
-      gpre[1] = ge.v[r0 + rq0];
+      gpre[1] = NL == 2 && ge.y2 != nullptr ? 0.0 : ge.v[r0 + rq0];
       gpre[2] = ge.q[r0 + rq0];
       if (NL == 1) gpre[3] = ge.p2[r0 + rq0];
     }
     constexpr int kPer = kSpmvNnz / kBlock;
+    // VPASS: v of this thread's row in each row pass of the block (at most kMaxRowsPerBlk rows; more than one pass only with
+    // G = 1, i.e. kBlock rows per pass -- what k_spmv_atl assumes with kAtlPass)
+    constexpr int kVPass = VPASS ? kMaxRowsPerBlk / kBlock : 1;
+    [[maybe_unused]] double vrow[kVPass] = {};
     int cidx[kPer];
     [[maybe_unused]] int slot[kPer];  // CSORT: where the entry's product goes (its position in the block's row-major order)
     double v[kPer];
@@ -337,15 +351,43 @@ __global__ __launch_bounds__(kBlock) void k_spmv(CsrView A, const double* __rest
       for (int k = 0; k < kPer; ++k) {
         xv[k] = *reinterpret_cast<const double2*>(x + (size_t)cidx[k] * 2);
       }
+      if constexpr (VPASS) {
+        if (VRAW || ge.y2 != nullptr) {  // (kernel-uniform) v of this thread's rows, one per row pass: see above
+          double yv[kPer];
+#pragma unroll
+          for (int k = 0; k < kPer; ++k) yv[k] = ge.y2[cidx[k]];
+#pragma unroll
+          for (int k = 0; k < kPer; ++k) prod[CSORT ? slot[k] : tid + k * kBlock] = v[k] * yv[k];
+          lds_barrier();
+#pragma unroll
+          for (int p = 0; p < kVPass; ++p) {
+            const int rr = p * rows_per_pass + g;
+            double a1[1] = {0.0};
+            if (rr < nr) {
+              const int a = (p == 0 ? seg_a0 : A.rowptr[r0 + rr]) - s, b = (p == 0 ? seg_b0 : A.rowptr[r0 + rr + 1]) - s;
+              row_segment_sum<1>(prod, a + gl, b, G, a1);
+            }
+            for (int off = G >> 1; off > 0; off >>= 1) a1[0] += __shfl_down(a1[0], off, 64);
+            vrow[p] = ge.vsign * a1[0] + 0.0;  // (the row epilogue of the single-lane product: ca acc + 0)
+          }
+          lds_barrier();  // (the buffer is rewritten below)
+        }
+      }
 #pragma unroll
       for (int k = 0; k < kPer; ++k)
         *reinterpret_cast<double2*>(prod + 2 * (CSORT ? slot[k] : tid + k * kBlock)) = make_double2(v[k] * xv[k].x, v[k] * xv[k].y);
     }
     lds_barrier();
     // phase 2: G lanes per row
-    for (int base = 0; base < nr; base += rows_per_pass) {
+    [[maybe_unused]] int pass = 0;
+    for (int base = 0; base < nr; base += rows_per_pass, ++pass) {
       const int rr = base + g;
       const bool valid = rr < nr;
+      [[maybe_unused]] double vsel = 0.0;  // VPASS: this pass's v
+      if constexpr (VPASS) {
+#pragma unroll
+        for (int p = 0; p < kVPass; ++p) vsel = p == pass ? vrow[p] : vsel;
+      }
       double acc[NL];
 #pragma unroll
       for (int l = 0; l < NL; ++l) acc[l] = 0.0;
@@ -365,7 +407,14 @@ __global__ __launch_bounds__(kBlock) void k_spmv(CsrView A, const double* __rest
           for (int l = 0; l < NL; ++l)
             if (act[l]) dst[l] = acc[l];
         } else if constexpr (GRAD && NL == 2) {
-          const double gi = base == 0 ? gpre[0] : ge.g[row], vi = base == 0 ? gpre[1] : ge.v[row], qi = base == 0 ? gpre[2] : ge.q[row];
+          const double gi = base == 0 ? gpre[0] : ge.g[row], qi = base == 0 ? gpre[2] : ge.q[row];
+          double vi;
+          if (ge.y2 != nullptr) {
+            vi = vsel;
+            ge.vout[row] = vi;
+          } else {
+            vi = base == 0 ? gpre[1] : ge.v[row];
+          }
           double gsi, gg;
           qp_grad_row(gi, acc[0], acc[NL - 1], vi, qi, ge.sigma, ge.rho, ge.eta, ge.x, ge.xk, row, gsi, gg);
           ge.gs[row] = gsi;
@@ -376,6 +425,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(CsrView A, const double* __rest
           ge.hv[row] = qp_hfin_row(vi, p1i, p2i, qi, acc[0], ge.sigma, ge.rho, ge.eta);
         } else {
           row_epilogue<NL>((size_t)row, acc, ca, cb, act, yin, yout, sq, base == 0 && yin != nullptr ? ypre : nullptr);
+          if constexpr (VRAW) ge.vout[row] = vsel;
         }
       }
     }
