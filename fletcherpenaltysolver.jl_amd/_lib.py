@@ -127,6 +127,7 @@ SYMBOLS = [
     ("fpsq_band_solve_two_least_squares", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, _DP]),
     ("fpsq_band_get_info", C.c_int, [_VP, C.POINTER(BandInfo)]),
     ("fpsq_band_qp_create", C.c_int, [_VP, _DP, _DP, _DP, C.POINTER(_VP)]),
+    ("fpsq_band_qp_create_csr", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.POINTER(_VP)]),
     ("fpsq_band_qp_destroy", C.c_int, [_VP]),
     ("fpsq_band_qp_objgrad", C.c_int, [_VP, _VP, _DP, _D, _D, _D, _DP, C.POINTER(C.c_double), _DP, _DP, _DP]),
     ("fpsq_band_qp_hprod", C.c_int, [_VP, _VP, _DP, _D, _D, _D, _I32, _DP]),

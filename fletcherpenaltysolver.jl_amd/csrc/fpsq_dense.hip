@@ -636,6 +636,12 @@ struct fpsq_band_qp_s {
   int lgA = 1, lgT = 1;                              // lanes per row of A / of A' (lane_group)
   int gridP = 1, gridE = 1;
   bool gather_g = false;  // FPSQ_BAND_QP_G=1: g formed at gather time instead of by k_bq_pack (A/B runs)
+  // fpsq_band_qp_create_csr: Q = diag(q) + R.  R = the off-diagonal part as full-row CSR (both triangles), tv = the n-vector
+  // the A' epilogue leaves p2 resp. Ptv in for the launch that subtracts R tv, partF = k_bq_pack_sq's partials of f, [gridR]
+  bool sparse_q = false;
+  int32_t *r_rowptr = nullptr, *r_colind = nullptr;
+  double *r_vals = nullptr, *tv = nullptr, *partF = nullptr;
+  int lgR = 1, gridR = 1;  // lanes per row of R (lane_group)
 };
 
 namespace {
@@ -1290,7 +1296,13 @@ void bq_launches(fpsq_band b, fpsq_band_qp qp, bool hp, const double* x, const d
   hipStream_t s = b->stream;
   const int n = (int)b->n, m = (int)b->m, mpad = (int)b->mpad;
   double* keep = b->o_q2;
-  if (!qp->gather_g) {
+  if (qp->sparse_q) {
+#define BQ_PACK_SQ(HP)                                                                                                   \
+  hipLaunchKernelGGL((k_bq_pack_sq<LG, HP>), dim3(qp->gridR), dim3(256), 0, s, qp->r_rowptr, qp->r_colind, qp->r_vals, x, \
+                     qp->q, qp->d, b->xn, qp->partF, n)
+    WITH_LANE_GROUP(qp->lgR, if (hp) BQ_PACK_SQ(true); else BQ_PACK_SQ(false);)
+#undef BQ_PACK_SQ
+  } else if (!qp->gather_g) {
     if (hp)
       hipLaunchKernelGGL(k_bq_pack<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, qp->q, qp->d, b->xn, n);
     else
@@ -1312,8 +1324,22 @@ void bq_launches(fpsq_band b, fpsq_band_qp qp, bool hp, const double* x, const d
   hipLaunchKernelGGL((k_bq_epilogue<LG, HP>), dim3(qp->gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, b->r2,   \
                      keep, b->reordered ? b->rperm : (const int32_t*)nullptr, x, xk, qp->q, qp->d, sigma, rho, eta, out, gs, \
                      ys, qp->partE, n, m)
-  WITH_LANE_GROUP(qp->lgT, if (hp) BQ_EPILOGUE(true); else BQ_EPILOGUE(false);)
+#define BQ_EPILOGUE_SQ(HP)                                                                                                 \
+  hipLaunchKernelGGL((k_bq_epilogue_sq<LG, HP>), dim3(qp->gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, b->r2, \
+                     keep, b->reordered ? b->rperm : (const int32_t*)nullptr, xk, qp->q, b->xn, sigma, rho, eta, out, gs, ys, \
+                     qp->tv, qp->partE, n, m)
+  if (!qp->sparse_q) {
+    WITH_LANE_GROUP(qp->lgT, if (hp) BQ_EPILOGUE(true); else BQ_EPILOGUE(false);)
+    return;
+  }
+  WITH_LANE_GROUP(qp->lgT, if (hp) BQ_EPILOGUE_SQ(true); else BQ_EPILOGUE_SQ(false);)
+  if (out) {  // out -= R p2 (objgrad) resp. R Ptv (hprod): the rows of tv are complete only now
+    WITH_LANE_GROUP(qp->lgR, hipLaunchKernelGGL(k_bq_jacmul<LG>, dim3(qp->gridR), dim3(256), 0, s, qp->r_rowptr, qp->r_colind,
+                                                qp->r_vals, (const int32_t*)nullptr, (const int32_t*)nullptr, -1.0, qp->tv, 1.0,
+                                                out, n))
+  }
 #undef BQ_EPILOGUE
+#undef BQ_EPILOGUE_SQ
 }
 }  // namespace
 
@@ -1354,9 +1380,94 @@ int fpsq_band_qp_create(fpsq_band b, const double* qdiag, const double* d, const
   return FPSQ_OK;
 }
 
+int fpsq_band_qp_create_csr(fpsq_band b, const int32_t* q_rowptr, const int32_t* q_colind, const double* q_vals,
+                            const double* d, const double* bvec, fpsq_band_qp* out) {
+  if (!b || !q_rowptr || !d || !bvec || !out) return FPSQ_ERR_ARG;
+  hipSetDevice(b->device);
+  const int64_t n = b->n;
+  auto bad = [&](const std::string& what) {
+    b->err = "band_qp_create_csr: " + what;
+    return FPSQ_ERR_ARG;
+  };
+  // Q on the host, once: the checks (the kernels read rows only, so an unsymmetric Q would give a wrong Hessian silently)
+  // and the split Q = diag(q) + R
+  std::vector<int32_t> rp((size_t)n + 1);
+  CHK(b, hipMemcpy(rp.data(), q_rowptr, ((size_t)n + 1) * 4, hipMemcpyDefault));
+  if (rp[0] != 0) return bad("rowptr[0] must be 0");
+  for (int64_t i = 0; i < n; ++i)
+    if (rp[i + 1] < rp[i]) return bad("rowptr decreases at row " + std::to_string(i));
+  const size_t nnz = (size_t)rp[n];
+  if (nnz && (!q_colind || !q_vals)) return FPSQ_ERR_ARG;
+  std::vector<int32_t> ci(nnz);
+  std::vector<double> va(nnz);
+  if (nnz) {
+    CHK(b, hipMemcpy(ci.data(), q_colind, nnz * 4, hipMemcpyDefault));
+    CHK(b, hipMemcpy(va.data(), q_vals, nnz * 8, hipMemcpyDefault));
+  }
+  std::vector<std::pair<int32_t, double>> ent(nnz);  // every row sorted by column
+  for (int64_t i = 0; i < n; ++i) {
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
+      if (ci[k] < 0 || ci[k] >= n)
+        return bad("column " + std::to_string(ci[k]) + " of row " + std::to_string(i) + " is out of range");
+      ent[k] = {ci[k], va[k]};
+    }
+    std::sort(ent.begin() + rp[i], ent.begin() + rp[i + 1],
+              [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& c) { return a.first < c.first; });
+    for (int32_t k = rp[i] + 1; k < rp[i + 1]; ++k)
+      if (ent[k].first == ent[k - 1].first)
+        return bad("duplicate entry (" + std::to_string(i) + ", " + std::to_string(ent[k].first) + ")");
+  }
+  std::vector<double> qd((size_t)n, 0.0), rv;
+  std::vector<int32_t> rrp((size_t)n + 1, 0), rci;
+  rv.reserve(nnz);
+  rci.reserve(nnz);
+  for (int64_t i = 0; i < n; ++i) {
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
+      const int32_t j = ent[k].first;
+      if (j == i) {
+        qd[i] = ent[k].second;
+        continue;
+      }
+      const auto lo = ent.begin() + rp[j], hi = ent.begin() + rp[j + 1];
+      const auto it = std::lower_bound(lo, hi, (int32_t)i,
+                                       [](const std::pair<int32_t, double>& a, int32_t col) { return a.first < col; });
+      if (it == hi || it->first != i)
+        return bad("the pattern is not symmetric: (" + std::to_string(i) + ", " + std::to_string(j) + ") has no transpose");
+      if (!(it->second == ent[k].second))
+        return bad("the values are not symmetric: Q(" + std::to_string(i) + ", " + std::to_string(j) + ") != Q(" +
+                   std::to_string(j) + ", " + std::to_string(i) + ")");
+      rci.push_back(j);
+      rv.push_back(ent[k].second);
+    }
+    rrp[i + 1] = (int32_t)rci.size();
+  }
+  fpsq_band_qp qp = nullptr;
+  if (int rc = fpsq_band_qp_create(b, qd.data(), d, bvec, &qp)) return rc;
+  const size_t rnz = rci.size();
+  qp->sparse_q = true;
+  qp->gather_g = false;  // (FPSQ_BAND_QP_G has no meaning here: g needs a product with R)
+  qp->lgR = lane_group((int64_t)rnz, n);
+  qp->gridR = bq_grid(n, qp->lgR);
+  if (hipMalloc((void**)&qp->r_rowptr, ((size_t)n + 1) * 4) != hipSuccess ||
+      hipMalloc((void**)&qp->r_colind, std::max<size_t>(rnz, 1) * 4) != hipSuccess ||
+      hipMalloc((void**)&qp->r_vals, std::max<size_t>(rnz, 1) * 8) != hipSuccess ||
+      hipMalloc((void**)&qp->tv, (size_t)n * 8) != hipSuccess ||
+      hipMalloc((void**)&qp->partF, (size_t)qp->gridR * 8) != hipSuccess ||
+      hipMemcpy(qp->r_rowptr, rrp.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      (rnz && (hipMemcpy(qp->r_colind, rci.data(), rnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(qp->r_vals, rv.data(), rnz * 8, hipMemcpyHostToDevice) != hipSuccess))) {
+    b->err = "band_qp_create_csr: cannot allocate or fill the objective Hessian";
+    fpsq_band_qp_destroy(qp);
+    return FPSQ_ERR_HIP;
+  }
+  *out = qp;
+  return FPSQ_OK;
+}
+
 int fpsq_band_qp_destroy(fpsq_band_qp qp) {
   if (!qp) return FPSQ_ERR_ARG;
-  for (double* p : {qp->q, qp->d, qp->bp, qp->partP, qp->partE})
+  for (void* p : {(void*)qp->q, (void*)qp->d, (void*)qp->bp, (void*)qp->partP, (void*)qp->partE, (void*)qp->r_rowptr,
+                  (void*)qp->r_colind, (void*)qp->r_vals, (void*)qp->tv, (void*)qp->partF})
     if (p) hipFree(p);
   delete qp;
   return FPSQ_OK;
@@ -1374,7 +1485,11 @@ int fpsq_band_qp_objgrad(fpsq_band b, fpsq_band_qp qp, const double* x, double s
   if (int rc = arg_in(b, eta > 0.0 ? xk : nullptr, b->in_b, n, &dxk)) return rc;
   double *dgx = arg_out(b, gx, b->o_p1), *dgs = arg_out(b, gs, b->o_p2), *dys = arg_out(b, ys, b->o_q1);
   bq_launches(b, qp, false, dx, dxk, sigma, rho, eta, dgx, dgs, dys);
-  hipLaunchKernelGGL(k_bq_phi, dim3(1), dim3(256), 0, b->stream, qp->partP, qp->gridP, qp->partE, qp->gridE, rho, eta, b->scal);
+  if (qp->sparse_q)
+    hipLaunchKernelGGL(k_bq_phi_sq, dim3(1), dim3(256), 0, b->stream, qp->partF, qp->gridR, qp->partP, qp->gridP, qp->partE,
+                       qp->gridE, rho, eta, b->scal);
+  else
+    hipLaunchKernelGGL(k_bq_phi, dim3(1), dim3(256), 0, b->stream, qp->partP, qp->gridP, qp->partE, qp->gridE, rho, eta, b->scal);
   if (int rc = arg_back(b, gx, dgx, n)) return rc;
   if (int rc = arg_back(b, gs, dgs, n)) return rc;
   if (int rc = arg_back(b, ys, dys, m)) return rc;

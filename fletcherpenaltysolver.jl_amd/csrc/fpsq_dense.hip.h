@@ -1133,6 +1133,8 @@ __global__ __launch_bounds__(256) void k_band_finish(const double* __restrict__ 
 
 // ---- device-resident equality-QP evaluations on the banded handle (fpsq_band_qp_*): f = 1/2 x' diag(q) x + d'x, c = A x - b.
 // An evaluation is [k_bq_pack] -> k_bq_prologue -> the two sweeps -> k_bq_epilogue [-> k_bq_phi]; A and A' are each read once.
+// With a sparse symmetric Q = diag(q) + R (fpsq_band_qp_create_csr; R = the off-diagonal part, full-row CSR) it is
+// k_bq_pack_sq -> k_bq_prologue -> the two sweeps -> k_bq_epilogue_sq -> k_bq_jacmul on R [-> k_bq_phi_sq]: R is read twice.
 // Both product kernels give a GROUP of LG lanes (a power of two <= 64, chosen from the mean row length when the model is
 // created) to a row, so that the value / index loads of a row are contiguous across lanes, and walk the row tiles with a
 // grid stride (the grid depends on the shape alone).  Sums are formed in a fixed order -- lanes by xor shuffles, waves in
@@ -1163,6 +1165,46 @@ __global__ __launch_bounds__(256) void k_bq_pack(const double* __restrict__ x, c
   if (HP) o = f64x2{xv, qv * xv};
   else o = f64x2{qv * xv + d[j], xv};
   *reinterpret_cast<f64x2*>(xg + (size_t)j * 2) = o;
+}
+
+// The same pair for Q = diag(q) + R, a lane group per row of R: with s = (R x)_j, objgrad {q_j x_j + d_j + s, x_j}, hprod
+// {v_j, q_j v_j + s}.  Objgrad only: part[blk] = this workgroup's slice of f = sum_j x_j (1/2 (Q x)_j + d_j).
+template <int LG, bool HP>
+__global__ __launch_bounds__(256) void k_bq_pack_sq(const int32_t* __restrict__ r_rowptr, const int32_t* __restrict__ r_colind,
+                                                    const double* __restrict__ r_vals, const double* __restrict__ x,
+                                                    const double* __restrict__ q, const double* __restrict__ d,
+                                                    double* __restrict__ xg, double* __restrict__ part, int n) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[4];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[1] = {0.0};
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s = 0.0;
+    if (j < n) {
+      const int e = r_rowptr[j + 1];
+      for (int k = r_rowptr[j] + l; k < e; k += LG) s += r_vals[k] * x[r_colind[k]];
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (l == 0 && j < n) {
+      const double xv = x[j], qv = q[j];
+      f64x2 o;
+      if (HP) {
+        o = f64x2{xv, qv * xv + s};
+      } else {
+        const double dv = d[j];
+        o = f64x2{qv * xv + dv + s, xv};
+        red[0] += xv * (0.5 * (qv * xv + s) + dv);
+      }
+      *reinterpret_cast<f64x2*>(xg + (size_t)j * 2) = o;
+    }
+  }
+  if (!HP) {
+    bq_block_sum(red, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+  }
 }
 
 // One pass over the (stored, i.e. row-permuted) CSR of A with two right-hand sides; row p of the stored order is written
@@ -1242,15 +1284,18 @@ __global__ __launch_bounds__(256) void k_bq_prologue(const int32_t* __restrict__
 //            caller's, null = identity) and leaves part[2 blk] = its slice of c.ys, part[2 blk + 1] = of |x - xk|^2.
 //   hprod:   Ptv_j = s1, p2_j = q_j v_j - s2, Hv_j = p2_j - q_j Ptv_j + 2 sigma Ptv_j + rho s3 + eta v_j   (out = Hv).
 // out, gs, ys, xk may be null.
-template <int LG, bool HP>
-__global__ __launch_bounds__(256) void k_bq_epilogue(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
-                                                     const double* __restrict__ t_vals, const double* __restrict__ y,
-                                                     const double* __restrict__ keep, const int32_t* __restrict__ rperm,
-                                                     const double* __restrict__ x, const double* __restrict__ xk,
-                                                     const double* __restrict__ q, const double* __restrict__ d, double sigma,
-                                                     double rho, double eta, double* __restrict__ out,
-                                                     double* __restrict__ gs, double* __restrict__ ys,
-                                                     double* __restrict__ part, int n, int m) {
+// SQ (Q = diag(q) + R): g_j resp. (Q v)_j and x_j resp. v_j come from the packed pair xg that k_bq_pack_sq wrote (x, d unused),
+// and tv_j = p2_j (objgrad) resp. Ptv_j (hprod) is left for the launch that subtracts R tv from out; the row's own terms,
+// -q_j p2_j resp. -q_j Ptv_j among them, are as above.
+template <int LG, bool HP, bool SQ>
+__device__ __forceinline__ void bq_epilogue_rows(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                 const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                 const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                 const double* __restrict__ x, const double* __restrict__ xk,
+                                                 const double* __restrict__ q, const double* __restrict__ d,
+                                                 const double* __restrict__ xg, double sigma, double rho, double eta,
+                                                 double* __restrict__ out, double* __restrict__ gs, double* __restrict__ ys,
+                                                 double* __restrict__ tv, double* __restrict__ part, int n, int m) {
   constexpr int RPB = 256 / LG;
   __shared__ double sh[8];
   const int g = threadIdx.x / LG, l = threadIdx.x % LG;
@@ -1277,11 +1322,22 @@ __global__ __launch_bounds__(256) void k_bq_epilogue(const int32_t* __restrict__
       s3 += __shfl_xor(s3, o);
     }
     if (l == 0 && j < n) {
-      const double xv = x[j], qv = q[j];
-      if (HP) {
-        out[j] = (qv * xv - s2) - qv * s1 + 2.0 * sigma * s1 + rho * s3 + eta * xv;
+      double xv, qv, u;  // u: g_j (objgrad), (Q v)_j (hprod)
+      if (SQ) {
+        const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)j * 2);
+        xv = HP ? t.x : t.y;
+        qv = q[j];
+        u = HP ? t.y : t.x;
+        tv[j] = HP ? s1 : -s2;
       } else {
-        const double gsv = (qv * xv + d[j]) - s1 - sigma * s2, p2 = -s2;
+        xv = x[j];
+        qv = q[j];
+        u = HP ? qv * xv : qv * xv + d[j];
+      }
+      if (HP) {
+        out[j] = (u - s2) - qv * s1 + 2.0 * sigma * s1 + rho * s3 + eta * xv;
+      } else {
+        const double gsv = u - s1 - sigma * s2, p2 = -s2;
         const double dx = eta > 0.0 ? xv - (xk ? xk[j] : 0.0) : 0.0;
         if (gs) gs[j] = gsv;
         if (out) out[j] = gsv + (sigma - qv) * p2 + rho * s3 + eta * dx;
@@ -1306,6 +1362,32 @@ __global__ __launch_bounds__(256) void k_bq_epilogue(const int32_t* __restrict__
   }
 }
 
+template <int LG, bool HP>
+__global__ __launch_bounds__(256) void k_bq_epilogue(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                     const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                     const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                     const double* __restrict__ x, const double* __restrict__ xk,
+                                                     const double* __restrict__ q, const double* __restrict__ d, double sigma,
+                                                     double rho, double eta, double* __restrict__ out,
+                                                     double* __restrict__ gs, double* __restrict__ ys,
+                                                     double* __restrict__ part, int n, int m) {
+  bq_epilogue_rows<LG, HP, false>(t_rowptr, t_colind, t_vals, y, keep, rperm, x, xk, q, d, nullptr, sigma, rho, eta, out, gs, ys,
+                                  nullptr, part, n, m);
+}
+
+template <int LG, bool HP>
+__global__ __launch_bounds__(256) void k_bq_epilogue_sq(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                        const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                        const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                        const double* __restrict__ xk, const double* __restrict__ q,
+                                                        const double* __restrict__ xg, double sigma, double rho, double eta,
+                                                        double* __restrict__ out, double* __restrict__ gs,
+                                                        double* __restrict__ ys, double* __restrict__ tv,
+                                                        double* __restrict__ part, int n, int m) {
+  bq_epilogue_rows<LG, HP, true>(t_rowptr, t_colind, t_vals, y, keep, rperm, nullptr, xk, q, nullptr, xg, sigma, rho, eta, out,
+                                 gs, ys, tv, part, n, m);
+}
+
 // The scalars of an objgrad from the workgroups' partials, each summed in index order (one workgroup: thread t takes a
 // contiguous run, then the fixed tree of bq_block_sum): out = {phi, f, c.c, c.ys, |x - xk|^2},
 // phi = f - c.ys + rho/2 c.c + eta/2 |x - xk|^2.
@@ -1318,6 +1400,32 @@ __global__ __launch_bounds__(256) void k_bq_phi(const double* __restrict__ partP
     red[0] += partP[(size_t)i * 2];
     red[1] += partP[(size_t)i * 2 + 1];
   }
+  for (int i = threadIdx.x * ce; i < min(nE, ((int)threadIdx.x + 1) * ce); ++i) {
+    red[2] += partE[(size_t)i * 2];
+    red[3] += partE[(size_t)i * 2 + 1];
+  }
+  bq_block_sum(red, sh);
+  if (threadIdx.x == 0) {
+    double phi = red[0] - red[2];
+    phi += 0.5 * rho * red[1];
+    phi += 0.5 * eta * red[3];
+    out[0] = phi;
+    out[1] = red[0];
+    out[2] = red[1];
+    out[3] = red[2];
+    out[4] = red[3];
+  }
+}
+
+// The same for Q = diag(q) + R: f comes from partF (the nF workgroups of k_bq_pack_sq, one double each), partP[2 i] is not read.
+__global__ __launch_bounds__(256) void k_bq_phi_sq(const double* __restrict__ partF, int nF, const double* __restrict__ partP,
+                                                   int nP, const double* __restrict__ partE, int nE, double rho, double eta,
+                                                   double* __restrict__ out) {
+  __shared__ double sh[16];
+  double red[4] = {0.0, 0.0, 0.0, 0.0};
+  const int cf = (nF + 255) / 256, cp = (nP + 255) / 256, ce = (nE + 255) / 256;
+  for (int i = threadIdx.x * cf; i < min(nF, ((int)threadIdx.x + 1) * cf); ++i) red[0] += partF[i];
+  for (int i = threadIdx.x * cp; i < min(nP, ((int)threadIdx.x + 1) * cp); ++i) red[1] += partP[(size_t)i * 2 + 1];
   for (int i = threadIdx.x * ce; i < min(nE, ((int)threadIdx.x + 1) * ce); ++i) {
     red[2] += partE[(size_t)i * 2];
     red[3] += partE[(size_t)i * 2 + 1];

@@ -26,6 +26,9 @@ class DeviceEqQP:
 
     def __init__(self, qp, sigma=1e3, rho=1.0, delta=0.0, eta=0.0, device=0, comm=None, halo=None, comm_route=None,
                  **opt_overrides):
+        if getattr(qp, "hess_vals", None) is not None:   # fpsq_qp_* know diag(q) alone: never evaluate the diagonal part silently
+            raise ValueError("DeviceEqQP (the iterative back-end) takes a diagonal objective Hessian only; a QP with a "
+                             "sparse Hessian (EqQP.hess_vals) runs on DeviceBandEqQP")
         self._lib = _lib.load()
         self.qp, self.sigma, self.rho, self.delta, self.eta = qp, sigma, rho, delta, eta
         opts = _lib.Options()
@@ -168,7 +171,8 @@ class DeviceEqQP:
 class DeviceBandEqQP:
     """The same device-resident eq-QP model on the DIRECT back-end: the block-banded factorisation of M = A A' + delta I
     (`fpsq_band_*`, the device counterpart of the reference's default `qds_solver = :ldlt`) with `fpsq_band_qp_objgrad` /
-    `fpsq_band_qp_hprod` on the CACHED factor.  The factor is rebuilt lazily -- once, at the next evaluation -- after
+    `fpsq_band_qp_hprod` on the CACHED factor.  A QP with a sparse symmetric objective Hessian (`EqQP.hess_*`,
+    `problems.with_sparse_hessian`) is evaluated with that Hessian (`fpsq_band_qp_create_csr`).  The factor is rebuilt lazily -- once, at the next evaluation -- after
     `set_delta` or `set_jacobian_values`; `info()["factorizations"]` counts how many this object has run.
     ldlt_tol / ldlt_r2: the dynamic regularisation of `LDLtSolver`, defaults as in qdsolver._DirectQDSolver (sqrt(eps),
     -sqrt(eps); "drop" drops a vanishing pivot).  Has the surface `fps_solve_device` uses on DeviceEqQP."""
@@ -192,9 +196,16 @@ class DeviceBandEqQP:
             self.ldlt_r2 = _ldlt_r2(ldlt_r2)
             self._check(self._lib.fpsq_band_set_regularization(h, self.ldlt_tol, -self.ldlt_r2))
             q = C.c_void_p()
-            self._check(self._lib.fpsq_band_qp_create(h, np.ascontiguousarray(qp.qdiag).ctypes.data,
-                                                      np.ascontiguousarray(qp.d).ctypes.data,
-                                                      np.ascontiguousarray(qp.b).ctypes.data, C.byref(q)))
+            dv, bv = np.ascontiguousarray(qp.d, dtype=np.float64), np.ascontiguousarray(qp.b, dtype=np.float64)
+            if getattr(qp, "hess_vals", None) is not None:   # sparse symmetric Q (full storage): fpsq_band_qp_create_csr
+                hrp = np.ascontiguousarray(qp.hess_rowptr, dtype=np.int32)
+                hci = np.ascontiguousarray(qp.hess_colind, dtype=np.int32)
+                hv = np.ascontiguousarray(qp.hess_vals, dtype=np.float64)
+                self._check(self._lib.fpsq_band_qp_create_csr(h, hrp.ctypes.data, hci.ctypes.data, hv.ctypes.data,
+                                                              dv.ctypes.data, bv.ctypes.data, C.byref(q)))
+            else:
+                self._check(self._lib.fpsq_band_qp_create(h, np.ascontiguousarray(qp.qdiag).ctypes.data, dv.ctypes.data,
+                                                          bv.ctypes.data, C.byref(q)))
             self._q = q
         except Exception:
             self.close()

@@ -621,6 +621,11 @@ class _DevicePenalty:
         d = torch.device("cuda", int(dev.device))
         qp = dev.qp
         self.q = torch.from_numpy(np.ascontiguousarray(qp.qdiag)).to(d)
+        self.Q = None   # the QP's sparse symmetric objective Hessian, when it has one (else Q = diag(q))
+        if getattr(qp, "hess_vals", None) is not None:
+            t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(d)  # noqa: E731
+            self.Q = torch.sparse_csr_tensor(t(qp.hess_rowptr, np.int64), t(qp.hess_colind, np.int64),
+                                             t(qp.hess_vals, np.float64), size=(qp.n, qp.n))
         self.d = torch.from_numpy(np.ascontiguousarray(qp.d)).to(d)
         self.b = torch.from_numpy(np.ascontiguousarray(qp.b)).to(d)
         self.ys = torch.empty(qp.m, dtype=torch.float64, device=d)
@@ -661,15 +666,18 @@ class _DevicePenalty:
     def state(self, x):
         if self._at is None or self._at is not x:
             self.objgrad_(x, self.scratch)
-        f = float(0.5 * (x @ (self.q * x)) + self.d @ x)
+        f = float(0.5 * (x @ self._qmul(x)) + self.d @ x)
         c = self._cons(x)
         return f, _nrm2(c), self.ys, _nrminf(c)
 
     def primal_inf(self, x):
         return _nrminf(self._cons(x))
 
+    def _qmul(self, x):
+        return self.q * x if self.Q is None else (self.Q @ x.unsqueeze(1)).squeeze(1)
+
     def grad_f(self, x):
-        return self.q * x + self.d
+        return self._qmul(x) + self.d
 
     def info(self):
         return {"objgrad_calls": self.nobjgrad, "hprod_calls": self.nhprod}

@@ -234,23 +234,36 @@ class HS7(_Model):
 
 
 class EqQPModel(_Model):
-    """Host view of problems.EqQP: f = 1/2 x'diag(q)x + d'x, c = Ax - b."""
+    """Host view of problems.EqQP: f = 1/2 x'Qx + d'x, c = Ax - b; Q = diag(q), or the QP's sparse symmetric Hessian."""
 
     def __init__(self, qp):
         super().__init__(qp.n, qp.m, qp.nnz, qp.x, name=qp.name)
         self.qp = qp
         self._A = qp.scipy_csr()
+        self._Q = qp.hess_csr() if getattr(qp, "hess_vals", None) is not None else None
         rows = np.repeat(np.arange(qp.m, dtype=np.int64), np.diff(qp.rowptr)) + 1
         self._struct = (rows, qp.colind.astype(np.int64) + 1)
 
-    def obj(self, x): return float(x @ (0.5 * self.qp.qdiag * x + self.qp.d))
-    def grad(self, x): return self.qp.qdiag * x + self.qp.d
+    def obj(self, x):
+        if self._Q is not None:
+            return float(x @ (0.5 * (self._Q @ x) + self.qp.d))
+        return float(x @ (0.5 * self.qp.qdiag * x + self.qp.d))
+
+    def grad(self, x):
+        if self._Q is not None:
+            return self._Q @ x + self.qp.d
+        return self.qp.qdiag * x + self.qp.d
+
     def cons(self, x): return self._A @ x - self.qp.b
     def jac_structure(self): return self._struct
     def jac_coord(self, x): return self.qp.vals
     def jtprod(self, x, v): return self._A.T @ v
     def jprod(self, x, v): return self._A @ v
-    def hprod(self, x, y, v, obj_weight=1.0): return obj_weight * self.qp.qdiag * np.asarray(v)
+
+    def hprod(self, x, y, v, obj_weight=1.0):
+        if self._Q is not None:
+            return obj_weight * (self._Q @ np.asarray(v))
+        return obj_weight * self.qp.qdiag * np.asarray(v)
 
 
 class TorchEqQPModel(EqQPModel):

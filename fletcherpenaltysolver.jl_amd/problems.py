@@ -5,11 +5,13 @@ specification of them.  Every random number comes from a counter-based generator
 ``u(seed, i, k) = splitmix64(seed ^ i*GOLDEN ^ k*C2) / 2**64`` so any language can reproduce the same bits.
 
 User model (what FletcherPenaltyNLP wraps, model-Fletcherpenaltynlp.jl:105-188):
-    f(x) = 1/2 x' diag(q) x + d' x,     c(x) = A x - b = 0
+    f(x) = 1/2 x' Q x + d' x,     c(x) = A x - b = 0,     Q = diag(q) unless the QP carries a sparse symmetric Hessian
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
@@ -50,10 +52,27 @@ class EqQP:
     b: np.ndarray
     x: np.ndarray  # evaluation point (infeasible)
     xhat: np.ndarray  # a feasible point, b = A xhat
+    # the objective Hessian Q when it is not diagonal: n x n CSR, 0-based int32, FULL symmetric storage (both triangles);
+    # None = diag(qdiag).  With a sparse Q, qdiag holds its diagonal.
+    hess_rowptr: Optional[np.ndarray] = None
+    hess_colind: Optional[np.ndarray] = None
+    hess_vals: Optional[np.ndarray] = None
 
     @property
     def nnz(self) -> int:
         return int(self.vals.size)
+
+    @property
+    def has_sparse_hessian(self) -> bool:
+        return self.hess_vals is not None
+
+    def hess_csr(self):
+        """Q as a scipy CSR matrix, whichever way the QP stores it."""
+        import scipy.sparse as sp
+
+        if self.hess_vals is None:
+            return sp.diags(self.qdiag, format="csr")
+        return sp.csr_matrix((self.hess_vals, self.hess_colind, self.hess_rowptr), shape=(self.n, self.n))
 
     def scipy_csr(self):
         import scipy.sparse as sp
@@ -78,6 +97,31 @@ def _finish(name, n, m, rowptr, colind, vals, seed) -> EqQP:
     b = A @ xhat
     x = xhat + 0.1 * (2.0 * uniform01(seed, idx, 4) - 1.0)
     return EqQP(name, n, m, rowptr.astype(np.int32), colind.astype(np.int32), vals, qdiag, d, b, x, xhat)
+
+
+def with_sparse_hessian(qp: EqQP, half_width: int = 2, seed: int = 4321) -> EqQP:
+    """A copy of `qp` whose objective Hessian is sparse, symmetric and banded -- the shape of a mass or stiffness matrix:
+    Q[i, j] = Q[j, i] = 2 u(seed, i * half_width + (j - i - 1), 21) - 1 for 0 < j - i <= half_width, except that every row
+    i with i % 7 == 3 has NO off-diagonal entry (its column neither), and Q[i, i] = 1 + 9 u(seed, i, 22) + sum_j |Q[i, j]|:
+    strictly diagonally dominant with a positive diagonal, hence positive definite.  `qdiag` holds the diagonal of Q."""
+    import scipy.sparse as sp
+
+    n, hw = qp.n, int(half_width)
+    assert hw >= 1
+    i = np.repeat(np.arange(n, dtype=np.int64), hw)
+    k = np.tile(np.arange(hw, dtype=np.int64), n)
+    j = i + k + 1
+    keep = (j < n) & (i % 7 != 3) & (j % 7 != 3)
+    i, j, k = i[keep], j[keep], k[keep]
+    v = 2.0 * uniform01(seed, i * hw + k, 21) - 1.0
+    absrow = np.bincount(i, np.abs(v), n) + np.bincount(j, np.abs(v), n)
+    idx = np.arange(n, dtype=np.int64)
+    diag = 1.0 + 9.0 * uniform01(seed, idx, 22) + absrow
+    Q = sp.coo_matrix((np.concatenate([v, v, diag]), (np.concatenate([i, j, idx]), np.concatenate([j, i, idx]))),
+                      shape=(n, n)).tocsr()
+    Q.sort_indices()
+    return dataclasses.replace(qp, name=f"{qp.name}-hess{hw}", qdiag=diag, hess_rowptr=Q.indptr.astype(np.int32),
+                               hess_colind=Q.indices.astype(np.int32), hess_vals=Q.data.astype(np.float64))
 
 
 def _stratified_rows(m, n, per_row, start, width, seed, diag_col=None, diag_boost=0.0):

@@ -397,10 +397,25 @@ int fpsq_band_get_info(fpsq_band b, fpsq_band_info *info);
  *                         NULL = the legacy default stream), each of the calls above and fpsq_band_factorize[_coo] first makes
  *                         the handle's stream wait (event, no host block) for everything enqueued on that stream so far.
  *                         Outputs are complete when a call returns, so there is no output-ordering switch.
+ *   fpsq_band_qp_create_csr  the same model with a SPARSE SYMMETRIC objective Hessian, f(x) = 1/2 x'Q x + d'x (a mass or
+ *                         stiffness matrix): Q is n x n in CSR, 0-based, FULL symmetric storage (both triangles), columns in
+ *                         any order, the diagonal may be absent (= 0); host or device pointers.  The constraints are linear, so
+ *                         the Lagrangian Hessian is Q and the two evaluations become (:403-437, :521-570)
+ *                           objgrad: g = Q x + d, gx = gs - Q p2 + sigma p2 + rho A'c + eta (x - xk), *fx with f = 1/2 x'Q x + d'x;
+ *                           hprod:   (p1, _, p2, _) = solve_two_least_squares(v, Q v), Hv = p2 - Q Ptv + 2 sigma Ptv
+ *                                    + rho A'(A v) + eta v   (hessian_approx = 1 again the same vector),
+ *                         everything else as above.  Checked once, on the host: an index out of range, a duplicate entry, a
+ *                         pattern or values that are not symmetric (Q_ij != Q_ji) give FPSQ_ERR_ARG with a message in
+ *                         fpsq_band_last_error(b) -- the kernels read rows only, so an unsymmetric Q would otherwise give a
+ *                         wrong Hessian silently.  fpsq_band_qp_objgrad / _hprod / _destroy take the object unchanged; an
+ *                         evaluation is two launches longer than on the diagonal model (Q = diag + R: R x resp. R v in front,
+ *                         R p2 resp. R Ptv behind the A' product) and as repeatable.  FPSQ_BAND_QP_G is ignored here.
  * Destroy a model before the handle it was created on.  FPSQ_BAND_QP_G=1 (read by fpsq_band_qp_create; A/B runs) forms g at
  * gather time in the A product instead of writing it first. */
 typedef struct fpsq_band_qp_s *fpsq_band_qp;
 int fpsq_band_qp_create(fpsq_band b, const double *qdiag, const double *d, const double *bvec, fpsq_band_qp *out);
+int fpsq_band_qp_create_csr(fpsq_band b, const int32_t *q_rowptr, const int32_t *q_colind, const double *q_vals,
+                            const double *d, const double *bvec, fpsq_band_qp *out);
 int fpsq_band_qp_destroy(fpsq_band_qp qp);
 int fpsq_band_qp_objgrad(fpsq_band b, fpsq_band_qp qp, const double *x, double sigma, double rho, double eta,
                          const double *xk, double *fx, double *gx, double *ys, double *gs);
