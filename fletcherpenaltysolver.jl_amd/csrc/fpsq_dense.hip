@@ -45,6 +45,11 @@ struct DirectCore {
   hipStream_t in_stream = nullptr;
   hipEvent_t ev_in = nullptr;
   double *scal = nullptr, *scal_host = nullptr;
+  // the sweeps over a tile of 16 right-hand-side columns (k_trsm_chain16), allocated by the first block call: right-hand
+  // sides / solutions [mpad][16], publication buffer [nb][4096] + abort word + ticket word, launch number
+  double *r16 = nullptr, *y16 = nullptr;
+  unsigned long long* blk_pub = nullptr;
+  unsigned int blk_seq = 0;
   std::vector<void*> allocs;
 };
 
@@ -204,6 +209,35 @@ void chain_sweeps(DirectCore* c, const double* M, int ld, int band_w, int chain_
   hipLaunchKernelGGL(k_trsv_chain<true>, dim3(nb), dim3(256), 0, c->stream, M, ld, c->invs, c->invsT, c->r2, c->y2, a);
   next();
   hipLaunchKernelGGL(k_trsv_chain<false>, dim3(nb), dim3(256), 0, c->stream, M, ld, c->invs, c->invsT, c->y2, c->r2, a);
+}
+
+// The same for a tile of 16 columns on the banded factor: c->r16 <- M^-1 c->r16 (via c->y16), one launch per sweep.  The
+// tickets of these launches are counted in the word behind this publication buffer's abort word, blk_seq numbers them.
+// chain16_setup allocates the buffers at the first call (they are freed with the handle); non-zero: failed.
+int chain16_setup(DirectCore* c) {
+  if (c->blk_pub) return FPSQ_OK;
+  const size_t pub_len = (size_t)c->nb * kBlkPub + 8;
+  unsigned long long* pub = nullptr;
+  if (dalloc(c, &c->r16, (size_t)c->mpad * kBlkCols) || dalloc(c, &c->y16, (size_t)c->mpad * kBlkCols) ||
+      dalloc(c, &pub, pub_len))
+    return FPSQ_ERR_HIP;
+  CHK(c, hipMemsetAsync(pub, 0, pub_len * 8, c->stream));
+  c->blk_pub = pub;
+  return FPSQ_OK;
+}
+
+void chain_sweeps16(DirectCore* c, const double* Mb, int band_w, int chain_safe, int chain_bw) {
+  const int nb = (int)c->nb;
+  ChainArgs a{c->blk_pub, 0, 0, nb, band_w, chain_safe, chain_bw, c->chain_err, c->blk_pub + (size_t)nb * kBlkPub + 1, 0};
+  auto next = [&] {
+    a.seq = ++c->blk_seq;
+    a.pubseq = c->chain_break ? ~a.seq : a.seq;
+    a.ticket_base = (unsigned long long)(c->blk_seq - 1) * nb;
+  };
+  next();
+  hipLaunchKernelGGL(k_trsm_chain16<true>, dim3(nb), dim3(256), 0, c->stream, Mb, c->invs, c->invsT, c->r16, c->y16, a);
+  next();
+  hipLaunchKernelGGL(k_trsm_chain16<false>, dim3(nb), dim3(256), 0, c->stream, Mb, c->invs, c->invsT, c->y16, c->r16, a);
 }
 
 // Start of a solve_two_* call: argument and state checks, the two right-hand sides staged in in_a / in_b (rhs1: n doubles,
@@ -622,6 +656,10 @@ struct fpsq_band_s : DirectCore {
   hipStream_t stream2 = nullptr;  // the second elimination chain
   hipEvent_t evA = nullptr, evB = nullptr;
   double* csr_in = nullptr;  // fpsq_band_create_coo: the CSR slots the sorted COO entries are summed into
+  // block entries (fpsq_band_*_block), allocated when first needed: the interleaved tile A multiplies [n][16], A v [mpad][8],
+  // Ptv [n][8] (sparse Q only), and the staging of host-resident blocks (rhs1 / V, rhs2, p1 / HV, p2: 8 n; q1, q2: 8 m)
+  double *blk_xg = nullptr, *blk_keep = nullptr, *blk_tv = nullptr;
+  double* blk_stage[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool have_vals = false;    // a factorisation has put the Jacobian's values into vals / t_vals (fpsq_band_jac_mul, fpsq_band_qp_*)
   fpsq_band_info info{};
 };
@@ -1543,5 +1581,164 @@ int fpsq_band_jac_mul(fpsq_band b, int32_t trans, double alpha, const double* x,
   if (int rc = arg_back(b, y, dy, ny)) return rc;
   CHK(b, hipStreamSynchronize(s));
   return FPSQ_OK;
+}
+}  // extern "C"
+
+// ------------------------------------------- block entries: a (k, n) block of vectors per call, 8 vectors per pass of the factor
+
+namespace {
+// One side of a block argument: in place when it lives on the handle's GPU, else through staging buffer `slot` (len doubles
+// per vector), a tile at a time
+struct BlockArg {
+  double* base = nullptr;
+  size_t len = 0;
+  bool dev = false;
+  double* stage = nullptr;
+  double* tile(int v0) const { return !base ? nullptr : dev ? base + (size_t)v0 * len : stage; }
+};
+
+int blk_arg(fpsq_band b, const double* p, size_t len, int slot, BlockArg* a) {
+  a->base = const_cast<double*>(p);
+  a->len = len;
+  if (!p) return FPSQ_OK;
+  a->dev = on_device(b, p);
+  if (!a->dev) {
+    if (!b->blk_stage[slot] && dalloc(b, &b->blk_stage[slot], len * kBlkVec)) return FPSQ_ERR_HIP;
+    a->stage = b->blk_stage[slot];
+  }
+  return FPSQ_OK;
+}
+
+// the tile's input as the kernels read it / the copy back of a staged output tile
+int blk_in(fpsq_band b, const BlockArg& a, int v0, int kt, const double** out) {
+  *out = a.tile(v0);
+  if (a.base && !a.dev)
+    CHK(b, hipMemcpyAsync(a.stage, a.base + (size_t)v0 * a.len, (size_t)kt * a.len * 8, hipMemcpyDefault, b->stream));
+  return FPSQ_OK;
+}
+
+int blk_back(fpsq_band b, const BlockArg& a, int v0, int kt) {
+  if (a.base && !a.dev)
+    CHK(b, hipMemcpyAsync(a.base + (size_t)v0 * a.len, a.stage, (size_t)kt * a.len * 8, hipMemcpyDefault, b->stream));
+  return FPSQ_OK;
+}
+
+// the buffers a block call needs: the sweeps' own and the tiles around them
+int blk_setup(fpsq_band b, bool keep, bool tv) {
+  if (int rc = chain16_setup(b)) return rc;
+  if (!b->blk_xg && dalloc(b, &b->blk_xg, (size_t)b->n * kBlkCols)) return FPSQ_ERR_HIP;
+  if (keep && !b->blk_keep && dalloc(b, &b->blk_keep, (size_t)b->mpad * kBlkVec)) return FPSQ_ERR_HIP;
+  if (tv && !b->blk_tv && dalloc(b, &b->blk_tv, (size_t)b->n * kBlkVec)) return FPSQ_ERR_HIP;
+  return FPSQ_OK;
+}
+
+// A xg into the sweeps' layout, then the two sweeps: the tile's solutions end up in b->r16
+void blk_solve_tile(fpsq_band b, int lgA, double* keep) {
+  WITH_LANE_GROUP(lgA, hipLaunchKernelGGL(k_bqb_prologue<LG>, dim3(bq_grid(b->mpad, lgA)), dim3(256), 0, b->stream, b->rowptr,
+                                          b->colind, b->vals, b->blk_xg, b->r16, keep, (int)b->m, (int)b->mpad))
+  chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
+}
+
+// end of a block call: eval_end with the text of a block sweep's expired wait
+int blk_end(fpsq_band b) {
+  const int rc = eval_end(b, 0, &b->info.last_solve_ms);
+  if (rc == FPSQ_ERR_TIMEOUT)
+    b->err = "block triangular sweep: a block's solution did not arrive (bounded wait expired); the single-vector entries "
+             "do not use this kernel";
+  return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int fpsq_band_solve_two_least_squares_block(fpsq_band b, int32_t k, const double* rhs1, const double* rhs2, double* p1,
+                                            double* q1, double* p2, double* q2) {
+  if (!b) return FPSQ_ERR_ARG;
+  if (k < 1 || !rhs1 || !rhs2) {
+    b->err = "band_solve_two_least_squares_block: k >= 1 and both right-hand-side blocks are required";
+    return FPSQ_ERR_ARG;
+  }
+  if (int rc = eval_begin(b)) return rc;
+  if (int rc = blk_setup(b, false, false)) return rc;
+  const size_t n = (size_t)b->n, m = (size_t)b->m;
+  BlockArg a1, a2, o1, oq1, o2, oq2;
+  if (blk_arg(b, rhs1, n, 0, &a1) || blk_arg(b, rhs2, n, 1, &a2) || blk_arg(b, p1, n, 2, &o1) || blk_arg(b, p2, n, 3, &o2) ||
+      blk_arg(b, q1, m, 4, &oq1) || blk_arg(b, q2, m, 5, &oq2))
+    return FPSQ_ERR_HIP;
+  const int lgA = lane_group(b->nnz, b->m), lgT = lane_group(b->nnz, b->n);
+  const int32_t* rperm = b->reordered ? b->rperm : nullptr;
+  for (int v0 = 0; v0 < k; v0 += kBlkVec) {
+    const int kt = std::min<int>(kBlkVec, k - v0);
+    const double *d1 = nullptr, *d2 = nullptr;
+    if (int rc = blk_in(b, a1, v0, kt, &d1)) return rc;
+    if (int rc = blk_in(b, a2, v0, kt, &d2)) return rc;
+    hipLaunchKernelGGL(k_bqb_pack<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, b->stream, d1, d2,
+                       (const double*)nullptr, b->blk_xg, (int)n, kt);
+    blk_solve_tile(b, lgA, nullptr);
+    WITH_LANE_GROUP(lgT, hipLaunchKernelGGL((k_bqb_epilogue<LG, 2>), dim3(bq_grid(b->n, lgT)), dim3(256), 0, b->stream,
+                                            b->t_rowptr, b->t_colind, b->t_vals, b->r16, (const double*)nullptr, rperm,
+                                            (const double*)nullptr, b->blk_xg, 0.0, 0.0, 0.0, o1.tile(v0), o2.tile(v0),
+                                            oq1.tile(v0), oq2.tile(v0), (double*)nullptr, (int)n, (int)m, kt))
+    for (const BlockArg* o : {&o1, &o2, &oq1, &oq2})
+      if (int rc = blk_back(b, *o, v0, kt)) return rc;
+  }
+  return blk_end(b);
+}
+
+int fpsq_band_qp_hprod_block(fpsq_band b, fpsq_band_qp qp, int32_t k, const double* V, double sigma, double rho, double eta,
+                             int32_t hessian_approx, double* HV) {
+  if (!b) return FPSQ_ERR_ARG;
+  if (!qp || qp->b != b || k < 1 || !V || !HV) {
+    b->err = "band_qp_hprod_block: a model of this handle, k >= 1 and both blocks are required";
+    return FPSQ_ERR_ARG;
+  }
+  if (hessian_approx != 1 && hessian_approx != 2) {
+    b->err = "band_qp_hprod_block: hessian_approx must be 1 or 2";
+    return FPSQ_ERR_ARG;
+  }
+  const size_t n = (size_t)b->n;
+  {
+    const uintptr_t lo = (uintptr_t)V, ho = (uintptr_t)HV, bytes = (uintptr_t)k * n * 8;
+    if (lo < ho + bytes && ho < lo + bytes) {
+      b->err = "band_qp_hprod_block: V and HV overlap";
+      return FPSQ_ERR_ARG;
+    }
+  }
+  if (int rc = eval_begin(b)) return rc;
+  if (int rc = blk_setup(b, true, qp->sparse_q)) return rc;
+  rho = rho > 0.0 ? rho : 0.0;
+  eta = eta > 0.0 ? eta : 0.0;
+  BlockArg av, ah;
+  if (blk_arg(b, V, n, 0, &av) || blk_arg(b, HV, n, 2, &ah)) return FPSQ_ERR_HIP;
+  const int32_t* rperm = b->reordered ? b->rperm : nullptr;
+  hipStream_t s = b->stream;
+  for (int v0 = 0; v0 < k; v0 += kBlkVec) {
+    const int kt = std::min<int>(kBlkVec, k - v0);
+    const double* dv = nullptr;
+    if (int rc = blk_in(b, av, v0, kt, &dv)) return rc;
+    double* dh = ah.tile(v0);
+    if (qp->sparse_q) {
+      WITH_LANE_GROUP(qp->lgR, hipLaunchKernelGGL(k_bqb_pack_sq<LG>, dim3(qp->gridR), dim3(256), 0, s, qp->r_rowptr,
+                                                  qp->r_colind, qp->r_vals, dv, qp->q, b->blk_xg, (int)n, kt))
+    } else {
+      hipLaunchKernelGGL(k_bqb_pack<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dv, (const double*)nullptr, qp->q,
+                         b->blk_xg, (int)n, kt);
+    }
+    blk_solve_tile(b, qp->lgA, b->blk_keep);
+#define BQB_EPILOGUE(MODE)                                                                                                   \
+  hipLaunchKernelGGL((k_bqb_epilogue<LG, MODE>), dim3(qp->gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, b->r16, \
+                     b->blk_keep, rperm, qp->q, b->blk_xg, sigma, rho, eta, dh, (double*)nullptr, (double*)nullptr,           \
+                     (double*)nullptr, b->blk_tv, (int)n, (int)b->m, kt)
+    if (qp->sparse_q) {
+      WITH_LANE_GROUP(qp->lgT, BQB_EPILOGUE(1))
+      WITH_LANE_GROUP(qp->lgR, hipLaunchKernelGGL(k_bqb_rsub<LG>, dim3(qp->gridR), dim3(256), 0, s, qp->r_rowptr, qp->r_colind,
+                                                  qp->r_vals, b->blk_tv, dh, (int)n, kt))
+    } else {
+      WITH_LANE_GROUP(qp->lgT, BQB_EPILOGUE(0))
+    }
+#undef BQB_EPILOGUE
+    if (int rc = blk_back(b, ah, v0, kt)) return rc;
+  }
+  return blk_end(b);
 }
 }  // extern "C"

@@ -948,6 +948,169 @@ __global__ __launch_bounds__(256) void k_trsv_chain(const double* __restrict__ L
   out[(size_t)b * (kDB * 2) + tid] = y;
 }
 
+// ---- the same chained sweep for a TILE of 16 right-hand-side columns (8 vectors x the two M-solves) on the banded factor,
+// on the fp64 matrix cores (fpsq_band_*_block).  A sweep of k_trsv_chain streams the whole factor for two columns; every
+// further column carried through the serial chain and the stream costs no byte of the factor.  The protocol is
+// k_trsv_chain's, unchanged: one launch per sweep, the block by ticket, chain_coupled for the band and the two chains, the
+// off-diagonal block requested before the look at Y_j, publication words that carry half a double and the launch number,
+// bounded waits that end in the error word and shorten behind the abort word.  What differs is the arithmetic of a link,
+// R_b -= L_bj Y_j with Y_j 128 x 16: 8 x 32 v_mfma_f64_16x16x4_f64, 64 per wave, each wave 32 rows of the block.
+// The summation index of an MFMA is free, and so is which 16 rows form a tile; both are chosen so that a lane's global
+// loads are 16 bytes wide and the fragments need no LDS:
+//   rows of wave T, tile e (0 / 1), lane l = (i = l & 15, g = l >> 4):  row(e, i) = 32 T + 2 i + e   (interleaved pairs);
+//   D register r of tile e is row 32 T + 2 (g + 4 r) + e, column i -- the layout of the right-hand side in registers, of a
+//   thread's 8 publication slots and of its 8 stores, the same in both sweeps;
+//   "by columns" (backward links, both diagonal solves: A[i][k] = X[k][row]): step s takes k = 4 s + g, one 16-byte load
+//   X[k][32 T + 2 i .. + 1] feeds both tiles -- 16 lanes read 256 contiguous bytes;
+//   "by rows" (forward links: A[i][k] = L[row][k]): chunk c of 8 columns, lane group g takes k = 8 c + 2 g + h (h = 0 / 1) from
+//   one 16-byte load per tile -- 4 lane groups read 64 contiguous bytes of each of 16 rows.
+// Y_j / the right-hand side for the diagonal solve go through LDS as [128][16] (a B fragment is 16 consecutive doubles per
+// lane group: conflict-free).  Every column of D is summed in the same fixed order whatever the other columns hold, so a
+// column's result does not depend on its position, on the other columns or on how many there are (short tiles are padded
+// with zero columns by the product kernels).  Even and odd steps accumulate separately (two dependent MFMA chains per
+// tile instead of one) and are added at the end of a link.  The diagonal solve skips the steps that lie wholly in the zero
+// triangle of the inverse (wave-uniform).
+// pub: [nb][4096] words -- slot q of thread t of block j at (q * 256 + t) * 2 --, [nb * 4096]: abort, [nb * 4096 + 1]: tickets.
+constexpr int kBlkCols = 16;                 // right-hand-side columns of a tile
+constexpr int kBlkPub = kDB * kBlkCols * 2;  // publication words of a block
+// this thread's 8 entries of block j's published tile, written to LDS in the [128][16] layout (bounded wait)
+__device__ __forceinline__ void chain_take16(const ChainArgs& c, int j, double* __restrict__ ylds, int row0, int col) {
+  const unsigned long long* p = c.pub + (size_t)j * kBlkPub + 2 * threadIdx.x;
+  unsigned long long* ab = c.pub + (size_t)c.nb * kBlkPub;
+  unsigned long long w[16];
+  int n = __hip_atomic_load(ab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == c.seq ? kChainPolls : 0;
+  for (;;) {
+    bool ok = true;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      w[2 * q] = __hip_atomic_load(p + q * 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      w[2 * q + 1] = __hip_atomic_load(p + q * 512 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) ok = ok && (unsigned int)w[q] == c.seq;
+    if (ok || ++n >= kChainPolls) break;
+    if ((n & 1023) == 0 && __hip_atomic_load(ab, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == c.seq) n = kChainPolls - 1;
+    __builtin_amdgcn_s_sleep(2);
+  }
+  if (n >= kChainPolls) {
+    __hip_atomic_store(ab, (unsigned long long)c.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(c.err, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q)  // slot q = tile q >> 2, register q & 3
+    ylds[(row0 + 8 * (q & 3) + (q >> 2)) * kBlkCols + col] =
+        __longlong_as_double((long long)((w[2 * q] & 0xffffffff00000000ull) | (w[2 * q + 1] >> 32)));
+}
+// P[e] = sum over the steps s0 <= s < s1 of the "by columns" product (xs[s] = X[4 s + g][row(0, i) .. + 1]) with the tile in ylds
+__device__ __forceinline__ void blk_mma_cols(const f64x2 (&xs)[32], const double* __restrict__ ylds, int g, int i, int s0,
+                                             int s1, f64x4 (&P)[2]) {
+  f64x4 a0[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, a1[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+#pragma unroll
+  for (int s = 0; s < 32; ++s) {
+    if (s >= s0 && s < s1) {  // (wave-uniform)
+      const double y = ylds[(4 * s + g) * kBlkCols + i];
+      a0[s & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xs[s][0], y, a0[s & 1], 0, 0, 0);
+      a1[s & 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xs[s][1], y, a1[s & 1], 0, 0, 0);
+    }
+  }
+  P[0] = a0[0] + a0[1];
+  P[1] = a1[0] + a1[1];
+}
+template <bool FORWARD>
+__global__ __launch_bounds__(256) void k_trsm_chain16(const double* __restrict__ Lm, const double* __restrict__ inv,
+                                                      const double* __restrict__ invT, const double* __restrict__ r,
+                                                      double* out, ChainArgs c) {
+  __shared__ double yk[kDB * kBlkCols];
+  __shared__ int ticket;
+  const int tid = threadIdx.x, lane = tid & 63, T = tid >> 6;
+  const int fi = lane & 15, fg = lane >> 4;
+  if (tid == 0)
+    ticket = (int)(__hip_atomic_fetch_add(c.ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - c.ticket_base);
+  __syncthreads();
+  const int b = FORWARD ? ticket : c.nb - 1 - ticket;
+  const int row0 = 32 * T + 2 * fg;  // row of register r of tile e: row0 + 8 r + e
+  // forward: Y = inv R = sum_k invT[k][row] R[k], k <= row;   backward: Q = inv' Y = sum_k inv[k][row] Y[k], k >= row
+  const int s0 = FORWARD ? 0 : 8 * T, s1 = FORWARD ? 8 * (T + 1) : 32;
+  f64x2 xs[32];
+  {
+    const double* Xc = (FORWARD ? invT : inv) + (size_t)b * kDB * kDB + (size_t)fg * kDB + 32 * T + 2 * fi;
+#pragma unroll
+    for (int s = 0; s < 32; ++s)
+      if (s >= s0 && s < s1) xs[s] = *reinterpret_cast<const f64x2*>(Xc + (size_t)(4 * s) * kDB);
+  }
+  f64x4 racc[2];
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) racc[e][q] = r[((size_t)b * kDB + row0 + 8 * q + e) * kBlkCols + fi];
+  const int band_w = c.band_w, w = band_w - 1;
+  if (FORWARD) {
+    for (int j = max(0, b - w); j < b; ++j) {
+      if (!chain_coupled(c, b, j)) continue;
+      // block (b, j) by rows: lb[e][cc] = L[32 T + 2 fi + e][8 cc + 2 fg .. + 1]
+      const double* Lb = Lm + ((size_t)b * band_w + (j - b + band_w - 1)) * kDB * kDB + (size_t)(32 * T + 2 * fi) * kDB + 2 * fg;
+      f64x2 lb[2][16];
+#pragma unroll
+      for (int cc = 0; cc < 16; ++cc) {
+        lb[0][cc] = *reinterpret_cast<const f64x2*>(Lb + 8 * cc);
+        lb[1][cc] = *reinterpret_cast<const f64x2*>(Lb + kDB + 8 * cc);
+      }
+      chain_take16(c, j, yk, row0, fi);
+      __syncthreads();
+      f64x4 a0[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, a1[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+#pragma unroll
+      for (int cc = 0; cc < 16; ++cc)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const double y = yk[(8 * cc + 2 * fg + h) * kBlkCols + fi];
+          a0[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(lb[0][cc][h], y, a0[h], 0, 0, 0);
+          a1[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(lb[1][cc][h], y, a1[h], 0, 0, 0);
+        }
+      racc[0] -= a0[0] + a0[1];
+      racc[1] -= a1[0] + a1[1];
+      __syncthreads();  // (yk is overwritten by the next link)
+    }
+  } else {
+    for (int j = min(c.nb - 1, b + w); j > b; --j) {
+      if (!chain_coupled(c, b, j)) continue;
+      // block (j, b) by columns: lb[s] = L[4 s + fg][32 T + 2 fi .. + 1]
+      const double* Lb = Lm + ((size_t)j * band_w + (b - j + band_w - 1)) * kDB * kDB + (size_t)fg * kDB + 32 * T + 2 * fi;
+      f64x2 lb[32];
+#pragma unroll
+      for (int s = 0; s < 32; ++s) lb[s] = *reinterpret_cast<const f64x2*>(Lb + (size_t)(4 * s) * kDB);
+      chain_take16(c, j, yk, row0, fi);
+      __syncthreads();
+      f64x4 P[2];
+      blk_mma_cols(lb, yk, fg, fi, 0, 32, P);
+      racc[0] -= P[0];
+      racc[1] -= P[1];
+      __syncthreads();  // (yk is overwritten by the next link)
+    }
+  }
+  // the diagonal solve: the right-hand side through LDS as the B operand
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) yk[(row0 + 8 * q + e) * kBlkCols + fi] = racc[e][q];
+  __syncthreads();
+  f64x4 Y[2];
+  blk_mma_cols(xs, yk, fg, fi, s0, s1, Y);
+  unsigned long long* p = c.pub + (size_t)b * kBlkPub + 2 * tid;
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const unsigned long long bits = (unsigned long long)__double_as_longlong(Y[e][q]);
+      __hip_atomic_store(p + (4 * e + q) * 512, (bits & 0xffffffff00000000ull) | c.pubseq, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(p + (4 * e + q) * 512 + 1, (bits << 32) | c.pubseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) out[((size_t)b * kDB + row0 + 8 * q + e) * kBlkCols + fi] = Y[e][q];
+}
+
 // ---- sparse direct path (fpsq_band): M = A A' + delta I of a BANDED sparse Jacobian as a block band
 // One workgroup per 128-row block I.  For each of its rows i in turn: scatter the row into a dense LDS window over its
 // column span, then every thread takes rows j <= i of the band (blocks I - bw .. I) and gathers its dot product with
@@ -1468,6 +1631,250 @@ __global__ __launch_bounds__(256) void k_bq_jacmul(const int32_t* __restrict__ r
     if (l == 0 && r < rows) {
       const int o = out_perm ? out_perm[r] : r;
       y[o] = alpha * s + (beta != 0.0 ? beta * y[o] : 0.0);
+    }
+  }
+}
+
+
+// ---- block forms of the product kernels (fpsq_band_qp_hprod_block, fpsq_band_solve_two_least_squares_block): a TILE of up
+// to kBlkVec vectors, vector v of a block at base + v * len (C-contiguous (k, len)), travels through A, the two sweeps
+// (k_trsm_chain16) and A' together, so every index and value of A, A' and R is read once per tile.  Between the kernels the
+// tile is interleaved: xg[j][2 v], xg[j][2 v + 1] = the pair A multiplies for vector v (hprod {v, Q v}, solve {rhs1, rhs2}),
+// r / y [p][2 v], [p][2 v + 1] = the right-hand sides / solutions of its two M-solves, keep[p][v] = A v, tv[j][v] = Ptv.
+// Columns kt <= v < kBlkVec of a short tile are ZERO from the pack on; every column is computed by the same instructions
+// in the same order whatever its neighbours hold, sums in a fixed order (lanes by xor shuffles), no atomics.
+constexpr int kBlkVec = kBlkCols / 2;
+
+// HP: xg[j] = {V[v][j], q[j] V[v][j]}_v;  else {V[v][j], W[v][j]}_v
+template <bool HP>
+__global__ __launch_bounds__(256) void k_bqb_pack(const double* __restrict__ V, const double* __restrict__ W,
+                                                  const double* __restrict__ q, double* __restrict__ xg, int n, int kt) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double qv = HP ? q[j] : 0.0;
+#pragma unroll
+  for (int v = 0; v < kBlkVec; ++v) {
+    f64x2 o = {0.0, 0.0};
+    if (v < kt) {
+      const double x = V[(size_t)v * n + j];
+      o = f64x2{x, HP ? qv * x : W[(size_t)v * n + j]};
+    }
+    *reinterpret_cast<f64x2*>(xg + (size_t)j * kBlkCols + 2 * v) = o;
+  }
+}
+
+// The hprod pair for Q = diag(q) + R, a lane group per row of R: xg[j] = {V[v][j], q[j] V[v][j] + (R V[v])_j}_v
+template <int LG>
+__global__ __launch_bounds__(256) void k_bqb_pack_sq(const int32_t* __restrict__ r_rowptr, const int32_t* __restrict__ r_colind,
+                                                     const double* __restrict__ r_vals, const double* __restrict__ V,
+                                                     const double* __restrict__ q, double* __restrict__ xg, int n, int kt) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s[kBlkVec];
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) s[v] = 0.0;
+    if (j < n) {
+      const int e = r_rowptr[j + 1];
+      for (int k = r_rowptr[j] + l; k < e; k += LG) {
+        const double a = r_vals[k];
+        const int c = r_colind[k];
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v)
+          if (v < kt) s[v] += a * V[(size_t)v * n + c];
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s[v] += __shfl_xor(s[v], o);
+    if (l == 0 && j < n) {
+      const double qv = q[j];
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        f64x2 o = {0.0, 0.0};
+        if (v < kt) {
+          const double x = V[(size_t)v * n + j];
+          o = f64x2{x, qv * x + s[v]};
+        }
+        *reinterpret_cast<f64x2*>(xg + (size_t)j * kBlkCols + 2 * v) = o;
+      }
+    }
+  }
+}
+
+// One pass over the stored CSR of A for the 16 columns of a tile: r[p] = (A xg)[p] where the sweeps read it (row p of the
+// stored order, zero on the padding), keep[p][v] = r[p][2 v] (= A v; null: not kept)
+template <int LG>
+__global__ __launch_bounds__(256) void k_bqb_prologue(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                      const double* __restrict__ vals, const double* __restrict__ xg,
+                                                      double* __restrict__ r, double* __restrict__ keep, int m, int mpad) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (mpad + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int p = tile * RPB + g;
+    double acc[kBlkCols];
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c) acc[c] = 0.0;
+    if (p < m) {
+      const int e = rowptr[p + 1];
+      for (int k = rowptr[p] + l; k < e; k += LG) {
+        const double a = vals[k];
+        const f64x2* t = reinterpret_cast<const f64x2*>(xg + (size_t)colind[k] * kBlkCols);
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v) {
+          const f64x2 u = t[v];
+          acc[2 * v] += a * u.x;
+          acc[2 * v + 1] += a * u.y;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
+    if (l == 0 && p < mpad) {  // (zero on the padding rows)
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        *reinterpret_cast<f64x2*>(r + (size_t)p * kBlkCols + 2 * v) = f64x2{acc[2 * v], acc[2 * v + 1]};
+        if (keep) keep[(size_t)p * kBlkVec + v] = acc[2 * v];
+      }
+    }
+  }
+}
+
+// One pass over the CSR of A' for a tile, the row epilogue per column.  Row j, vector v: s1 = (A'q1)_j, s2 = (A'q2)_j with
+// y[p] = {q1, q2}_v the sweeps' solution in the stored order, s3 = (A'keep)_j.
+//   MODE 0 (hprod, Q = diag(q)), 1 (hprod, Q = diag(q) + R):  Ptv = s1, p2 = (Q v)_j - s2 with {v_j, (Q v)_j} from xg,
+//       o1[v][j] = Hv = p2 - q_j Ptv + 2 sigma Ptv + rho s3 + eta v_j;  MODE 1 leaves tv[j][v] = Ptv for k_bqb_rsub.
+//   MODE 2 (solve_two_least_squares):  o1[v][j] = p1 = rhs1 - s1, o2[v][j] = p2 = rhs2 - s2 (null: not produced), and the
+//       workgroup writes its slice of oq1[v] = q1, oq2[v] = q2 in the caller's row order (rperm: stored row -> the caller's,
+//       null = identity; null outputs: not produced).
+template <int LG, int MODE>
+__global__ __launch_bounds__(256) void k_bqb_epilogue(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                      const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                      const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                      const double* __restrict__ q, const double* __restrict__ xg, double sigma,
+                                                      double rho, double eta, double* __restrict__ o1, double* __restrict__ o2,
+                                                      double* __restrict__ oq1, double* __restrict__ oq2,
+                                                      double* __restrict__ tv, int n, int m, int kt) {
+  constexpr int RPB = 256 / LG;
+  constexpr bool HP = MODE != 2;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s12[kBlkCols], s3[kBlkVec];
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c) s12[c] = 0.0;
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) s3[v] = 0.0;
+    if (j < n) {
+      const int e = t_rowptr[j + 1];
+      for (int k = t_rowptr[j] + l; k < e; k += LG) {
+        const double a = t_vals[k];
+        const int p = t_colind[k];
+        const f64x2* t = reinterpret_cast<const f64x2*>(y + (size_t)p * kBlkCols);
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v) {
+          const f64x2 u = t[v];
+          s12[2 * v] += a * u.x;
+          s12[2 * v + 1] += a * u.y;
+        }
+        if (HP) {
+          const f64x2* kp = reinterpret_cast<const f64x2*>(keep + (size_t)p * kBlkVec);
+#pragma unroll
+          for (int v = 0; v < kBlkVec / 2; ++v) {
+            const f64x2 u = kp[v];
+            s3[2 * v] += a * u.x;
+            s3[2 * v + 1] += a * u.y;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s12[c] += __shfl_xor(s12[c], o);
+    if (HP) {
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v)
+#pragma unroll
+        for (int o = LG / 2; o > 0; o >>= 1) s3[v] += __shfl_xor(s3[v], o);
+    }
+    if (l == 0 && j < n) {
+      const double qv = HP ? q[j] : 0.0;
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)j * kBlkCols + 2 * v);
+        const double s1 = s12[2 * v], s2 = s12[2 * v + 1];
+        if (MODE == 1) tv[(size_t)j * kBlkVec + v] = s1;
+        if (v < kt) {
+          if (HP) {
+            o1[(size_t)v * n + j] = (t.y - s2) - qv * s1 + 2.0 * sigma * s1 + rho * s3[v] + eta * t.x;
+          } else {
+            if (o1) o1[(size_t)v * n + j] = t.x - s1;
+            if (o2) o2[(size_t)v * n + j] = t.y - s2;
+          }
+        }
+      }
+    }
+  }
+  if (MODE == 2 && (oq1 || oq2)) {
+    const int64_t chunk = ((int64_t)m + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < m ? lo + chunk : m;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+      const size_t dst = (size_t)(rperm ? rperm[p] : p);
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        if (v < kt) {
+          const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * kBlkCols + 2 * v);
+          if (oq1) oq1[(size_t)v * m + dst] = t.x;
+          if (oq2) oq2[(size_t)v * m + dst] = t.y;
+        }
+      }
+    }
+  }
+}
+
+// out[v][j] -= (R tv[.][v])_j for the vectors of a tile, a lane group per row of R (tv: [n][kBlkVec], complete only after the
+// A' pass)
+template <int LG>
+__global__ __launch_bounds__(256) void k_bqb_rsub(const int32_t* __restrict__ r_rowptr, const int32_t* __restrict__ r_colind,
+                                                  const double* __restrict__ r_vals, const double* __restrict__ tv, double* out,
+                                                  int n, int kt) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s[kBlkVec];
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) s[v] = 0.0;
+    if (j < n) {
+      const int e = r_rowptr[j + 1];
+      for (int k = r_rowptr[j] + l; k < e; k += LG) {
+        const double a = r_vals[k];
+        const f64x2* t = reinterpret_cast<const f64x2*>(tv + (size_t)r_colind[k] * kBlkVec);
+#pragma unroll
+        for (int v = 0; v < kBlkVec / 2; ++v) {
+          const f64x2 u = t[v];
+          s[2 * v] += a * u.x;
+          s[2 * v + 1] += a * u.y;
+        }
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s[v] += __shfl_xor(s[v], o);
+    if (l == 0 && j < n) {
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v)
+        if (v < kt) out[(size_t)v * n + j] -= s[v];
     }
   }
 }

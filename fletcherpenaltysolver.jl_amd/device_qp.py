@@ -269,6 +269,56 @@ class DeviceBandEqQP:
         return self._check(self._lib.fpsq_band_qp_hprod(self._h, self._q, _lib.ptr(v), self.sigma, self.rho, self.eta,
                                                         int(hessian_approx), _lib.ptr(Hv)))
 
+    @staticmethod
+    def _block(a, name, k, length, optional=False):
+        """A block argument: a C-contiguous float64 (k, length) numpy array or torch tensor (k = None: any k >= 1); returns k."""
+        if a is None:
+            if optional:
+                return k
+            raise ValueError(f"{name}: a block is required")
+        shape = tuple(getattr(a, "shape", ()))
+        if isinstance(a, np.ndarray):
+            ok, contiguous = a.dtype == np.float64, a.flags["C_CONTIGUOUS"]
+        elif hasattr(a, "data_ptr"):
+            import torch
+
+            ok, contiguous = a.dtype == torch.float64, a.is_contiguous()
+        else:
+            raise ValueError(f"{name}: a numpy array or a torch tensor is expected, not {type(a).__name__}")
+        if not ok:
+            raise ValueError(f"{name}: float64 expected, got {a.dtype}")
+        if len(shape) != 2 or shape[1] != length or shape[0] < 1 or (k is not None and shape[0] != k):
+            want = f"({'k' if k is None else k}, {length})"
+            raise ValueError(f"{name}: shape {want} expected, got {shape}")
+        if not contiguous:
+            raise ValueError(f"{name}: the block must be C-contiguous")
+        return shape[0]
+
+    def hprod_block(self, V, HV, hessian_approx=2):
+        """Row j of HV = hprod on row j of V: (k, n) float64 blocks, numpy arrays or torch tensors (host or device), C-contiguous
+        (include/fpsq.h fpsq_band_qp_hprod_block: 8 vectors per pass over the factor).  Returns rc."""
+        k = self._block(V, "V", None, self.qp.n)
+        self._block(HV, "HV", k, self.qp.n)
+        if self._factor():
+            return self._fact_rc
+        self._order(V, HV)
+        return self._check(self._lib.fpsq_band_qp_hprod_block(self._h, self._q, k, _lib.ptr(V), self.sigma, self.rho,
+                                                              self.eta, int(hessian_approx), _lib.ptr(HV)))
+
+    def solve_two_least_squares_block(self, rhs1, rhs2, p1=None, q1=None, p2=None, q2=None):
+        """Row j of (p1, q1, p2, q2) = solve_two_least_squares(rhs1[j], rhs2[j]) on the cached factor: (k, n) / (k, m) float64
+        blocks as in hprod_block; outputs that are None are not produced (fpsq_band_solve_two_least_squares_block)."""
+        n, m = self.qp.n, self.qp.m
+        k = self._block(rhs1, "rhs1", None, n)
+        self._block(rhs2, "rhs2", k, n)
+        for a, name, length in ((p1, "p1", n), (q1, "q1", m), (p2, "p2", n), (q2, "q2", m)):
+            self._block(a, name, k, length, optional=True)
+        if self._factor():
+            return self._fact_rc
+        self._order(rhs1, rhs2, p1, q1, p2, q2)
+        return self._check(self._lib.fpsq_band_solve_two_least_squares_block(
+            self._h, k, _lib.ptr(rhs1), _lib.ptr(rhs2), _lib.ptr(p1), _lib.ptr(q1), _lib.ptr(p2), _lib.ptr(q2)))
+
     def jac_mul(self, trans, alpha, x, beta, y):
         """y = alpha op(A) x + beta y with the model's Jacobian (fpsq_band_jac_mul; trans = 0: A, 1: A')."""
         self._factor()   # (the values reach the handle with a factorisation)

@@ -424,6 +424,28 @@ int fpsq_band_qp_hprod(fpsq_band b, fpsq_band_qp qp, const double *v, double sig
 int fpsq_band_jac_mul(fpsq_band b, int32_t trans, double alpha, const double *x, double beta, double *y);
 int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
 
+/* ---- block entries on the cached banded factor: k vectors per call.  A triangular sweep streams the whole factor whether it
+ * carries one vector or several, so these entries carry a TILE of 8 vectors (16 right-hand-side columns: the two M-solves of
+ * each) through one pair of sweeps on the fp64 matrix cores; k > 8 is processed in successive tiles of 8.
+ * A block is k vectors stored one after the other: vector j of an n-block starts at base + j * n (a C-contiguous (k, n) array);
+ * q1 / q2 are (k, m).  Pointers are host or device; device-resident blocks are read and written in place.  Calls are
+ * synchronous (outputs complete on return), honour fpsq_band_set_input_stream, update last_solve_ms and return
+ * FPSQ_ERR_STATE without a valid factor.  Work buffers (16 (n + 2 mpad) + 8 mpad doubles, the publication buffer, 8 n more for
+ * a sparse Q, staging for host-resident blocks) are allocated at the first block call and freed with the handle.
+ *   fpsq_band_solve_two_least_squares_block  column j = fpsq_band_solve_two_least_squares(rhs1[j], rhs2[j]); any of p1, q1, p2, q2
+ *                         may be NULL and is then not produced.  k < 1 or a NULL right-hand side: FPSQ_ERR_ARG.
+ *   fpsq_band_qp_hprod_block  column j = fpsq_band_qp_hprod on V[j], for both models (fpsq_band_qp_create, _create_csr);
+ *                         hessian_approx 1 and 2 give the same bits, any other value FPSQ_ERR_ARG, as do k < 1, a NULL block
+ *                         and V / HV ranges that overlap (message in fpsq_band_last_error).
+ * DETERMINISM: a column's result is bitwise independent of k, of the column's position in the block and of what the other
+ * columns hold (short tiles are padded with zero columns; every column's sums have a fixed order), and repeatable from call
+ * to call.  It is NOT bitwise the single-vector entry's -- the matrix-core sweep sums in another order than the vector-unit
+ * sweep --; both meet the same bar against the exact solve. */
+int fpsq_band_solve_two_least_squares_block(fpsq_band b, int32_t k, const double *rhs1, const double *rhs2, double *p1,
+                                            double *q1, double *p2, double *q2);
+int fpsq_band_qp_hprod_block(fpsq_band b, fpsq_band_qp qp, int32_t k, const double *V, double sigma, double rho, double eta,
+                             int32_t hessian_approx, double *HV);
+
 /* ---- introspection for benchmarks / profiling */
 typedef struct {
   int64_t n, m, nnz;
