@@ -1,0 +1,758 @@
+// fpsq_band.hip.h -- kernels of the banded direct back-end alone (fpsq_band.hip): formation of M = A A' + delta I as a
+// block band (k_band_form*), the CSR products and vector kernels around the M-solves (k_csr_mv2, k_gather_d, k_band_rhs,
+// k_band_finish), the device-resident eq-QP evaluations (k_bq_*) and their block forms (k_bqb_*).
+#pragma once
+#include "fpsq_direct.hip.h"
+
+namespace fpsq {
+
+// ---- sparse direct path (fpsq_band): M = A A' + delta I of a BANDED sparse Jacobian as a block band
+// One workgroup per 128-row block I.  For each of its rows i in turn: scatter the row into a dense LDS window over its
+// column span, then every thread takes rows j <= i of the band (blocks I - bw .. I) and gathers its dot product with
+// row i from the window (columns outside the window contribute nothing); M(i, j) goes to block (I, j / 128).
+// (A wave per band row with unit-stride loads was measured slower -- 114 against 87 ms at the headline size: the loop
+// over the band rows then is a chain of dependent loads, whereas 256 threads walking 256 rows keep 256 streams in flight.)
+// Deterministic (fixed summation order, no atomics).  rowspan[i] = {first column, last column} of row i.
+__global__ __launch_bounds__(256) void k_band_form(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                   const double* __restrict__ vals, const int2* __restrict__ rowspan,
+                                                   int m, int mpad, int band_w, double delta, double* Mb, int span) {
+  extern __shared__ __attribute__((aligned(16))) double win[];  // two windows of `span` doubles: rows i and i + 1
+  const int I = blockIdx.x, tid = threadIdx.x;
+  for (int k = tid; k < 2 * span; k += 256) win[k] = 0.0;
+  __syncthreads();
+  const int i0 = I * kDB;
+  const int bw = band_w - 1;
+  const int jlo = max(0, I - bw) * kDB;
+  // TWO rows of the block per pass: every entry of a band row that is loaded serves both dot products (the band rows
+  // are re-read from L2 once per pass: 64 instead of 128 times)
+  for (int ii = 0; ii < kDB; ii += 2) {
+    const int i = i0 + ii;
+    double* Mrow0 = Mb + ((size_t)I * band_w) * kDB * kDB + (size_t)ii * kDB;  // row ii of block (I, I - bw)
+    double* Mrow1 = Mrow0 + kDB;
+    if (i >= m) {  // padding: identity
+      if (tid == 0 && i < mpad) Mrow0[(size_t)bw * kDB * kDB + ii] = 1.0;
+      if (tid == 0 && i + 1 < mpad) Mrow1[(size_t)bw * kDB * kDB + ii + 1] = 1.0;
+      continue;
+    }
+    const bool two = i + 1 < m;
+    const int s0 = rowptr[i], e0 = rowptr[i + 1], e1 = two ? rowptr[i + 2] : e0;
+    const int2 sp0 = rowspan[i];
+    const int2 sp1 = two ? rowspan[i + 1] : int2{1, 0};  // (an empty span: nothing matches)
+    for (int k = s0 + tid; k < e0; k += 256) win[colind[k] - sp0.x] = vals[k];
+    for (int k = e0 + tid; k < e1; k += 256) win[span + colind[k] - sp1.x] = vals[k];
+    __syncthreads();
+    for (int j = jlo + tid; j <= i + 1 && j < m; j += 256) {
+      const int js = rowptr[j], je = rowptr[j + 1];
+      double a0 = 0.0, a1 = 0.0;
+      for (int k = js; k < je; ++k) {
+        const int c = colind[k];
+        const double v = vals[k];
+        if (c >= sp0.x && c <= sp0.y) a0 += v * win[c - sp0.x];
+        if (c >= sp1.x && c <= sp1.y) a1 += v * win[span + c - sp1.x];
+      }
+      const size_t off = (size_t)((j >> 7) - I + bw) * kDB * kDB + (j & 127);
+      if (j <= i) Mrow0[off] = j == i ? a0 + delta : a0;
+      if (two) Mrow1[off] = j == i + 1 ? a1 + delta : a1;  // (j <= i + 1 by the loop bound)
+    }
+    if (!two && i + 1 < mpad && tid == 0) Mrow1[(size_t)bw * kDB * kDB + ii + 1] = 1.0;  // first padding row
+    __syncthreads();
+    for (int k = s0 + tid; k < e0; k += 256) win[colind[k] - sp0.x] = 0.0;
+    for (int k = e0 + tid; k < e1; k += 256) win[span + colind[k] - sp1.x] = 0.0;
+    __syncthreads();
+  }
+}
+
+// The same band by COLUMNS of A (the default when A has no duplicate entries): M(i, :) = sum over the entries (i, k) of
+// row i of a_ik * A(:, k), the column read from the transposed structure.  Only structurally non-zero products are
+// formed -- nnz(A) * (entries per column) of them, 1e8 at the headline size against the 1.6e10 gather-FMAs of the
+// row-pair scheme above (61 ms there).  One workgroup per 128-row block, R rows of it per pass, one group of G = 256 / R
+// lanes per row with a dense accumulator row of W * 128 doubles in LDS (columns (I - bw) * 128 ...): the lanes of a
+// group take the entries of ONE column of A (distinct rows j: no two lanes touch the same accumulator), the entries
+// (i, k) of the row are taken in CSR order, four columns' loads in flight -- so every M(i, j) is summed in a fixed order,
+// no atomics.  The accumulator rows are then written out whole (zeros included) and cleared.
+__global__ __launch_bounds__(256) void k_band_form_t(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                     const double* __restrict__ vals, const int32_t* __restrict__ t_rowptr,
+                                                     const int32_t* __restrict__ t_rowind, const double* __restrict__ t_vals,
+                                                     int m, int mpad, int band_w, double delta, double* Mb, int R) {
+  extern __shared__ __attribute__((aligned(16))) double win[];  // R accumulator rows of band_w * 128
+  const int I = blockIdx.x, tid = threadIdx.x;
+  const int G = 256 / R, g = tid / G, gl = tid % G;
+  const int roww = band_w * kDB;
+  const int base = (I - (band_w - 1)) * kDB;  // global column of accumulator entry 0 (may be negative: never touched)
+  for (int k = tid; k < R * roww; k += 256) win[k] = 0.0;
+  __syncthreads();
+  double* acc = win + (size_t)g * roww - base;  // acc[j], j a global row index of A = column of M
+  for (int pass = 0; pass < kDB; pass += R) {
+    const int i = I * kDB + pass + g;
+    if (i < m) {
+      const int s = rowptr[i], e = rowptr[i + 1];
+      for (int t = s; t < e; t += 4) {
+        int us[4], ue[4], j[4];
+        double a[4], v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const bool ok = t + q < e;
+          const int k = colind[ok ? t + q : s];
+          a[q] = ok ? vals[t + q] : 0.0;
+          us[q] = t_rowptr[k];
+          ue[q] = ok ? t_rowptr[k + 1] : us[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int u = us[q] + gl;
+          const bool ok = u < ue[q];
+          j[q] = ok ? t_rowind[u] : INT32_MAX;
+          v[q] = ok ? t_vals[u] : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if (j[q] <= i) acc[j[q]] += a[q] * v[q];
+          for (int u = us[q] + gl + G; u < ue[q]; u += G) {  // columns longer than the group
+            const int jj = t_rowind[u];
+            if (jj <= i) acc[jj] += a[q] * t_vals[u];
+          }
+        }
+      }
+      if (gl == 0) acc[i] += delta;
+    } else if (i < mpad && gl == 0) {
+      acc[i] = 1.0;  // padding: identity
+    }
+    __syncthreads();
+    for (int idx = tid; idx < R * roww; idx += 256) {
+      const int r = idx / roww, e = idx - r * roww;
+      Mb[((size_t)I * band_w + (e >> 7)) * kDB * kDB + (size_t)(pass + r) * kDB + (e & 127)] = win[idx];
+      win[idx] = 0.0;
+    }
+    __syncthreads();
+  }
+}
+
+// y[r][0..1] = sum_k vals[k] x[colind[k]][0..1] over row r of a CSR matrix (two interleaved right-hand sides); one
+// thread per row
+__global__ __launch_bounds__(256) void k_csr_mv2(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                 const double* __restrict__ vals, const double* __restrict__ x, double* y,
+                                                 int rows) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= rows) return;
+  double a0 = 0.0, a1 = 0.0;
+  for (int k = rowptr[r]; k < rowptr[r + 1]; ++k) {
+    const double v = vals[k];
+    const double2 xv = *reinterpret_cast<const double2*>(x + (size_t)colind[k] * 2);
+    a0 += v * xv.x;
+    a1 += v * xv.y;
+  }
+  y[(size_t)r * 2] = a0;
+  y[(size_t)r * 2 + 1] = a1;
+}
+
+__global__ __launch_bounds__(256) void k_gather_d(const double* __restrict__ in, const int32_t* __restrict__ perm,
+                                                  double* __restrict__ out, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = in[perm[i]];
+}
+
+// r[i] = {ag[i][0], sb * b[i]} on rows < m, zero on the padding (the right-hand sides of the two M-solves)
+__global__ __launch_bounds__(256) void k_band_rhs(const double* __restrict__ ag, int col, const double* b, double sb,
+                                                  double* r, int m, int mpad, int both) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= mpad) return;
+  const bool in = i < m;
+  r[(size_t)i * 2] = in ? ag[(size_t)i * 2] : 0.0;
+  r[(size_t)i * 2 + 1] = in ? (both ? ag[(size_t)i * 2 + 1] : sb * b[i]) : 0.0;
+  (void)col;
+}
+
+// p1 = a0 - atq[.][0];  p2 = (a1 ? a1 : 0) - atq[.][1]
+__global__ __launch_bounds__(256) void k_band_finish(const double* __restrict__ atq, const double* a0, const double* a1,
+                                                     double* p1, double* p2, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  p1[i] = a0[i] - atq[(size_t)i * 2];
+  p2[i] = (a1 ? a1[i] : 0.0) - atq[(size_t)i * 2 + 1];
+}
+
+// ---- device-resident equality-QP evaluations on the banded handle (fpsq_band_qp_*): f = 1/2 x' diag(q) x + d'x, c = A x - b.
+// An evaluation is [k_bq_pack] -> k_bq_prologue -> the two sweeps -> k_bq_epilogue [-> k_bq_phi]; A and A' are each read once.
+// With a sparse symmetric Q = diag(q) + R (fpsq_band_qp_create_csr; R = the off-diagonal part, full-row CSR) it is
+// k_bq_pack_sq -> k_bq_prologue -> the two sweeps -> k_bq_epilogue_sq -> k_bq_jacmul on R [-> k_bq_phi_sq]: R is read twice.
+// Both product kernels give a GROUP of LG lanes (a power of two <= 64, chosen from the mean row length when the model is
+// created) to a row, so that the value / index loads of a row are contiguous across lanes, and walk the row tiles with a
+// grid stride (the grid depends on the shape alone).  Sums are formed in a fixed order -- lanes by xor shuffles, waves in
+// index order, workgroups in index order by k_bq_phi -- so an evaluation is bitwise repeatable; no floating-point atomics.
+
+// sum of v[i] over the 256 threads of the workgroup, in thread 0 (sh: 4 * N doubles); every thread must call it
+template <int N>
+__device__ __forceinline__ void bq_block_sum(double (&v)[N], double* sh) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+    for (int o = 32; o > 0; o >>= 1) v[i] += __shfl_xor(v[i], o);
+  if ((threadIdx.x & 63) == 0)
+    for (int i = 0; i < N; ++i) sh[(threadIdx.x >> 6) * N + i] = v[i];
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int i = 0; i < N; ++i) v[i] = ((sh[i] + sh[N + i]) + sh[2 * N + i]) + sh[3 * N + i];
+  __syncthreads();
+}
+
+// the two vectors A multiplies, interleaved: objgrad (HP = false) {g = q x + d, x}; hprod (HP = true) {v, q v}
+template <bool HP>
+__global__ __launch_bounds__(256) void k_bq_pack(const double* __restrict__ x, const double* __restrict__ q,
+                                                 const double* __restrict__ d, double* __restrict__ xg, int n) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double xv = x[j], qv = q[j];
+  f64x2 o;
+  if (HP) o = f64x2{xv, qv * xv};
+  else o = f64x2{qv * xv + d[j], xv};
+  *reinterpret_cast<f64x2*>(xg + (size_t)j * 2) = o;
+}
+
+// The same pair for Q = diag(q) + R, a lane group per row of R: with s = (R x)_j, objgrad {q_j x_j + d_j + s, x_j}, hprod
+// {v_j, q_j v_j + s}.  Objgrad only: part[blk] = this workgroup's slice of f = sum_j x_j (1/2 (Q x)_j + d_j).
+template <int LG, bool HP>
+__global__ __launch_bounds__(256) void k_bq_pack_sq(const int32_t* __restrict__ r_rowptr, const int32_t* __restrict__ r_colind,
+                                                    const double* __restrict__ r_vals, const double* __restrict__ x,
+                                                    const double* __restrict__ q, const double* __restrict__ d,
+                                                    double* __restrict__ xg, double* __restrict__ part, int n) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[4];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[1] = {0.0};
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s = 0.0;
+    if (j < n) {
+      const int e = r_rowptr[j + 1];
+      for (int k = r_rowptr[j] + l; k < e; k += LG) s += r_vals[k] * x[r_colind[k]];
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (l == 0 && j < n) {
+      const double xv = x[j], qv = q[j];
+      f64x2 o;
+      if (HP) {
+        o = f64x2{xv, qv * xv + s};
+      } else {
+        const double dv = d[j];
+        o = f64x2{qv * xv + dv + s, xv};
+        red[0] += xv * (0.5 * (qv * xv + s) + dv);
+      }
+      *reinterpret_cast<f64x2*>(xg + (size_t)j * 2) = o;
+    }
+  }
+  if (!HP) {
+    bq_block_sum(red, sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+  }
+}
+
+// One pass over the (stored, i.e. row-permuted) CSR of A with two right-hand sides; row p of the stored order is written
+// where the sweeps read it, r[p] = {A g, -(A x - b)} (objgrad) or {A v, A (q v)} (hprod), zero on the padding, and keep[p] = c
+// resp. A v stays for the epilogue.  GM: the right-hand sides are formed at gather time from x, q, d instead of being read
+// from the packed xg.  Objgrad only: part[2 blk] = this workgroup's slice of f = x.(1/2 q x + d), part[2 blk + 1] = of c.c.
+template <int LG, bool HP, bool GM>
+__global__ __launch_bounds__(256) void k_bq_prologue(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                     const double* __restrict__ vals, const double* __restrict__ xg,
+                                                     const double* __restrict__ x, const double* __restrict__ q,
+                                                     const double* __restrict__ d, const double* __restrict__ bp,
+                                                     double* __restrict__ r, double* __restrict__ keep,
+                                                     double* __restrict__ part, int m, int mpad, int n) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[8];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[2] = {0.0, 0.0};
+  const int ntiles = (mpad + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int p = tile * RPB + g;
+    double a0 = 0.0, a1 = 0.0;
+    if (p < m) {
+      const int e = rowptr[p + 1];
+      for (int k = rowptr[p] + l; k < e; k += LG) {
+        const double a = vals[k];
+        const int c = colind[k];
+        double u0, u1;
+        if (GM) {
+          const double xv = x[c], qv = q[c];
+          u0 = HP ? xv : qv * xv + d[c];
+          u1 = HP ? qv * xv : xv;
+        } else {
+          const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)c * 2);
+          u0 = t.x;
+          u1 = t.y;
+        }
+        a0 += a * u0;
+        a1 += a * u1;
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) {
+      a0 += __shfl_xor(a0, o);
+      a1 += __shfl_xor(a1, o);
+    }
+    if (l == 0 && p < mpad) {  // (a0 = a1 = 0 on the padding rows)
+      double r1 = a1, kv = a0;
+      if (!HP && p < m) {
+        kv = a1 - bp[p];
+        r1 = -kv;
+        red[1] += kv * kv;
+      }
+      *reinterpret_cast<f64x2*>(r + (size_t)p * 2) = f64x2{a0, r1};
+      keep[p] = kv;
+    }
+  }
+  if (!HP) {
+    const int64_t chunk = ((int64_t)n + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
+      const double xv = x[j];
+      red[0] += xv * (0.5 * q[j] * xv + d[j]);
+    }
+    bq_block_sum(red, sh);
+    if (threadIdx.x == 0) {
+      part[(size_t)blockIdx.x * 2] = red[0];
+      part[(size_t)blockIdx.x * 2 + 1] = red[1];
+    }
+  }
+}
+
+// One pass over the CSR of A' (column indices = stored rows of A) on the three vectors the evaluation needs -- q1, q2 (the
+// sweeps' solution y[p] = {q1, q2}, read in the stored order: un-permuted on the fly) and keep (c resp. A v) -- with the row
+// epilogue fused in.  Row j, s1 = (A'q1)_j, s2 = (A'q2)_j, s3 = (A'keep)_j:
+//   objgrad: gs_j = g_j - s1 - sigma s2, p2_j = -s2, grad_j = gs_j + (sigma - q_j) p2_j + rho s3 + eta (x_j - xk_j);
+//            the workgroup also writes its slice of ys = q1 + sigma q2 in the caller's row order (rperm: stored row -> the
+//            caller's, null = identity) and leaves part[2 blk] = its slice of c.ys, part[2 blk + 1] = of |x - xk|^2.
+//   hprod:   Ptv_j = s1, p2_j = q_j v_j - s2, Hv_j = p2_j - q_j Ptv_j + 2 sigma Ptv_j + rho s3 + eta v_j   (out = Hv).
+// out, gs, ys, xk may be null.
+// SQ (Q = diag(q) + R): g_j resp. (Q v)_j and x_j resp. v_j come from the packed pair xg that k_bq_pack_sq wrote (x, d unused),
+// and tv_j = p2_j (objgrad) resp. Ptv_j (hprod) is left for the launch that subtracts R tv from out; the row's own terms,
+// -q_j p2_j resp. -q_j Ptv_j among them, are as above.
+template <int LG, bool HP, bool SQ>
+__device__ __forceinline__ void bq_epilogue_rows(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                 const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                 const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                 const double* __restrict__ x, const double* __restrict__ xk,
+                                                 const double* __restrict__ q, const double* __restrict__ d,
+                                                 const double* __restrict__ xg, double sigma, double rho, double eta,
+                                                 double* __restrict__ out, double* __restrict__ gs, double* __restrict__ ys,
+                                                 double* __restrict__ tv, double* __restrict__ part, int n, int m) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[8];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[2] = {0.0, 0.0};
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (j < n) {
+      const int e = t_rowptr[j + 1];
+      for (int k = t_rowptr[j] + l; k < e; k += LG) {
+        const double a = t_vals[k];
+        const int p = t_colind[k];
+        const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * 2);
+        s1 += a * t.x;
+        s2 += a * t.y;
+        s3 += a * keep[p];
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) {
+      s1 += __shfl_xor(s1, o);
+      s2 += __shfl_xor(s2, o);
+      s3 += __shfl_xor(s3, o);
+    }
+    if (l == 0 && j < n) {
+      double xv, qv, u;  // u: g_j (objgrad), (Q v)_j (hprod)
+      if (SQ) {
+        const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)j * 2);
+        xv = HP ? t.x : t.y;
+        qv = q[j];
+        u = HP ? t.y : t.x;
+        tv[j] = HP ? s1 : -s2;
+      } else {
+        xv = x[j];
+        qv = q[j];
+        u = HP ? qv * xv : qv * xv + d[j];
+      }
+      if (HP) {
+        out[j] = (u - s2) - qv * s1 + 2.0 * sigma * s1 + rho * s3 + eta * xv;
+      } else {
+        const double gsv = u - s1 - sigma * s2, p2 = -s2;
+        const double dx = eta > 0.0 ? xv - (xk ? xk[j] : 0.0) : 0.0;
+        if (gs) gs[j] = gsv;
+        if (out) out[j] = gsv + (sigma - qv) * p2 + rho * s3 + eta * dx;
+        red[1] += dx * dx;
+      }
+    }
+  }
+  if (!HP) {
+    const int64_t chunk = ((int64_t)m + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < m ? lo + chunk : m;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+      const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * 2);
+      const double yv = t.x + sigma * t.y;
+      if (ys) ys[rperm ? rperm[p] : p] = yv;
+      red[0] += keep[p] * yv;
+    }
+    bq_block_sum(red, sh);
+    if (threadIdx.x == 0) {
+      part[(size_t)blockIdx.x * 2] = red[0];
+      part[(size_t)blockIdx.x * 2 + 1] = red[1];
+    }
+  }
+}
+
+template <int LG, bool HP>
+__global__ __launch_bounds__(256) void k_bq_epilogue(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                     const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                     const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                     const double* __restrict__ x, const double* __restrict__ xk,
+                                                     const double* __restrict__ q, const double* __restrict__ d, double sigma,
+                                                     double rho, double eta, double* __restrict__ out,
+                                                     double* __restrict__ gs, double* __restrict__ ys,
+                                                     double* __restrict__ part, int n, int m) {
+  bq_epilogue_rows<LG, HP, false>(t_rowptr, t_colind, t_vals, y, keep, rperm, x, xk, q, d, nullptr, sigma, rho, eta, out, gs, ys,
+                                  nullptr, part, n, m);
+}
+
+template <int LG, bool HP>
+__global__ __launch_bounds__(256) void k_bq_epilogue_sq(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                        const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                        const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                        const double* __restrict__ xk, const double* __restrict__ q,
+                                                        const double* __restrict__ xg, double sigma, double rho, double eta,
+                                                        double* __restrict__ out, double* __restrict__ gs,
+                                                        double* __restrict__ ys, double* __restrict__ tv,
+                                                        double* __restrict__ part, int n, int m) {
+  bq_epilogue_rows<LG, HP, true>(t_rowptr, t_colind, t_vals, y, keep, rperm, nullptr, xk, q, nullptr, xg, sigma, rho, eta, out,
+                                 gs, ys, tv, part, n, m);
+}
+
+// The scalars of an objgrad from the workgroups' partials, each summed in index order (one workgroup: thread t takes a
+// contiguous run, then the fixed tree of bq_block_sum): out = {phi, f, c.c, c.ys, |x - xk|^2},
+// phi = f - c.ys + rho/2 c.c + eta/2 |x - xk|^2.
+__global__ __launch_bounds__(256) void k_bq_phi(const double* __restrict__ partP, int nP, const double* __restrict__ partE,
+                                                int nE, double rho, double eta, double* __restrict__ out) {
+  __shared__ double sh[16];
+  double red[4] = {0.0, 0.0, 0.0, 0.0};
+  const int cp = (nP + 255) / 256, ce = (nE + 255) / 256;
+  for (int i = threadIdx.x * cp; i < min(nP, ((int)threadIdx.x + 1) * cp); ++i) {
+    red[0] += partP[(size_t)i * 2];
+    red[1] += partP[(size_t)i * 2 + 1];
+  }
+  for (int i = threadIdx.x * ce; i < min(nE, ((int)threadIdx.x + 1) * ce); ++i) {
+    red[2] += partE[(size_t)i * 2];
+    red[3] += partE[(size_t)i * 2 + 1];
+  }
+  bq_block_sum(red, sh);
+  if (threadIdx.x == 0) {
+    double phi = red[0] - red[2];
+    phi += 0.5 * rho * red[1];
+    phi += 0.5 * eta * red[3];
+    out[0] = phi;
+    out[1] = red[0];
+    out[2] = red[1];
+    out[3] = red[2];
+    out[4] = red[3];
+  }
+}
+
+// The same for Q = diag(q) + R: f comes from partF (the nF workgroups of k_bq_pack_sq, one double each), partP[2 i] is not read.
+__global__ __launch_bounds__(256) void k_bq_phi_sq(const double* __restrict__ partF, int nF, const double* __restrict__ partP,
+                                                   int nP, const double* __restrict__ partE, int nE, double rho, double eta,
+                                                   double* __restrict__ out) {
+  __shared__ double sh[16];
+  double red[4] = {0.0, 0.0, 0.0, 0.0};
+  const int cf = (nF + 255) / 256, cp = (nP + 255) / 256, ce = (nE + 255) / 256;
+  for (int i = threadIdx.x * cf; i < min(nF, ((int)threadIdx.x + 1) * cf); ++i) red[0] += partF[i];
+  for (int i = threadIdx.x * cp; i < min(nP, ((int)threadIdx.x + 1) * cp); ++i) red[1] += partP[(size_t)i * 2 + 1];
+  for (int i = threadIdx.x * ce; i < min(nE, ((int)threadIdx.x + 1) * ce); ++i) {
+    red[2] += partE[(size_t)i * 2];
+    red[3] += partE[(size_t)i * 2 + 1];
+  }
+  bq_block_sum(red, sh);
+  if (threadIdx.x == 0) {
+    double phi = red[0] - red[2];
+    phi += 0.5 * rho * red[1];
+    phi += 0.5 * eta * red[3];
+    out[0] = phi;
+    out[1] = red[0];
+    out[2] = red[1];
+    out[3] = red[2];
+    out[4] = red[3];
+  }
+}
+
+// y[o(r)] = alpha sum_k vals[k] x[i(colind[k])] + beta y[o(r)] over the rows of a CSR matrix, a lane group per row;
+// in_perm / out_perm (null = identity) translate stored rows of A to the caller's: A x takes out_perm, A' x takes in_perm
+template <int LG>
+__global__ __launch_bounds__(256) void k_bq_jacmul(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                   const double* __restrict__ vals, const int32_t* __restrict__ in_perm,
+                                                   const int32_t* __restrict__ out_perm, double alpha,
+                                                   const double* __restrict__ x, double beta, double* y, int rows) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (rows + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int r = tile * RPB + g;
+    double s = 0.0;
+    if (r < rows) {
+      const int e = rowptr[r + 1];
+      for (int k = rowptr[r] + l; k < e; k += LG) {
+        const int c = colind[k];
+        s += vals[k] * x[in_perm ? in_perm[c] : c];
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (l == 0 && r < rows) {
+      const int o = out_perm ? out_perm[r] : r;
+      y[o] = alpha * s + (beta != 0.0 ? beta * y[o] : 0.0);
+    }
+  }
+}
+
+
+// ---- block forms of the product kernels (fpsq_band_qp_hprod_block, fpsq_band_solve_two_least_squares_block): a TILE of up
+// to kBlkVec vectors, vector v of a block at base + v * len (C-contiguous (k, len)), travels through A, the two sweeps
+// (k_trsm_chain16) and A' together, so every index and value of A, A' and R is read once per tile.  Between the kernels the
+// tile is interleaved: xg[j][2 v], xg[j][2 v + 1] = the pair A multiplies for vector v (hprod {v, Q v}, solve {rhs1, rhs2}),
+// r / y [p][2 v], [p][2 v + 1] = the right-hand sides / solutions of its two M-solves, keep[p][v] = A v, tv[j][v] = Ptv.
+// Columns kt <= v < kBlkVec of a short tile are ZERO from the pack on; every column is computed by the same instructions
+// in the same order whatever its neighbours hold, sums in a fixed order (lanes by xor shuffles), no atomics.
+constexpr int kBlkVec = kBlkCols / 2;
+
+// HP: xg[j] = {V[v][j], q[j] V[v][j]}_v;  else {V[v][j], W[v][j]}_v
+template <bool HP>
+__global__ __launch_bounds__(256) void k_bqb_pack(const double* __restrict__ V, const double* __restrict__ W,
+                                                  const double* __restrict__ q, double* __restrict__ xg, int n, int kt) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double qv = HP ? q[j] : 0.0;
+#pragma unroll
+  for (int v = 0; v < kBlkVec; ++v) {
+    f64x2 o = {0.0, 0.0};
+    if (v < kt) {
+      const double x = V[(size_t)v * n + j];
+      o = f64x2{x, HP ? qv * x : W[(size_t)v * n + j]};
+    }
+    *reinterpret_cast<f64x2*>(xg + (size_t)j * kBlkCols + 2 * v) = o;
+  }
+}
+
+// The hprod pair for Q = diag(q) + R, a lane group per row of R: xg[j] = {V[v][j], q[j] V[v][j] + (R V[v])_j}_v
+template <int LG>
+__global__ __launch_bounds__(256) void k_bqb_pack_sq(const int32_t* __restrict__ r_rowptr, const int32_t* __restrict__ r_colind,
+                                                     const double* __restrict__ r_vals, const double* __restrict__ V,
+                                                     const double* __restrict__ q, double* __restrict__ xg, int n, int kt) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s[kBlkVec];
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) s[v] = 0.0;
+    if (j < n) {
+      const int e = r_rowptr[j + 1];
+      for (int k = r_rowptr[j] + l; k < e; k += LG) {
+        const double a = r_vals[k];
+        const int c = r_colind[k];
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v)
+          if (v < kt) s[v] += a * V[(size_t)v * n + c];
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s[v] += __shfl_xor(s[v], o);
+    if (l == 0 && j < n) {
+      const double qv = q[j];
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        f64x2 o = {0.0, 0.0};
+        if (v < kt) {
+          const double x = V[(size_t)v * n + j];
+          o = f64x2{x, qv * x + s[v]};
+        }
+        *reinterpret_cast<f64x2*>(xg + (size_t)j * kBlkCols + 2 * v) = o;
+      }
+    }
+  }
+}
+
+// One pass over the stored CSR of A for the 16 columns of a tile: r[p] = (A xg)[p] where the sweeps read it (row p of the
+// stored order, zero on the padding), keep[p][v] = r[p][2 v] (= A v; null: not kept)
+template <int LG>
+__global__ __launch_bounds__(256) void k_bqb_prologue(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                      const double* __restrict__ vals, const double* __restrict__ xg,
+                                                      double* __restrict__ r, double* __restrict__ keep, int m, int mpad) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (mpad + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int p = tile * RPB + g;
+    double acc[kBlkCols];
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c) acc[c] = 0.0;
+    if (p < m) {
+      const int e = rowptr[p + 1];
+      for (int k = rowptr[p] + l; k < e; k += LG) {
+        const double a = vals[k];
+        const f64x2* t = reinterpret_cast<const f64x2*>(xg + (size_t)colind[k] * kBlkCols);
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v) {
+          const f64x2 u = t[v];
+          acc[2 * v] += a * u.x;
+          acc[2 * v + 1] += a * u.y;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
+    if (l == 0 && p < mpad) {  // (zero on the padding rows)
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        *reinterpret_cast<f64x2*>(r + (size_t)p * kBlkCols + 2 * v) = f64x2{acc[2 * v], acc[2 * v + 1]};
+        if (keep) keep[(size_t)p * kBlkVec + v] = acc[2 * v];
+      }
+    }
+  }
+}
+
+// One pass over the CSR of A' for a tile, the row epilogue per column.  Row j, vector v: s1 = (A'q1)_j, s2 = (A'q2)_j with
+// y[p] = {q1, q2}_v the sweeps' solution in the stored order, s3 = (A'keep)_j.
+//   MODE 0 (hprod, Q = diag(q)), 1 (hprod, Q = diag(q) + R):  Ptv = s1, p2 = (Q v)_j - s2 with {v_j, (Q v)_j} from xg,
+//       o1[v][j] = Hv = p2 - q_j Ptv + 2 sigma Ptv + rho s3 + eta v_j;  MODE 1 leaves tv[j][v] = Ptv for k_bqb_rsub.
+//   MODE 2 (solve_two_least_squares):  o1[v][j] = p1 = rhs1 - s1, o2[v][j] = p2 = rhs2 - s2 (null: not produced), and the
+//       workgroup writes its slice of oq1[v] = q1, oq2[v] = q2 in the caller's row order (rperm: stored row -> the caller's,
+//       null = identity; null outputs: not produced).
+template <int LG, int MODE>
+__global__ __launch_bounds__(256) void k_bqb_epilogue(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
+                                                      const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                      const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                      const double* __restrict__ q, const double* __restrict__ xg, double sigma,
+                                                      double rho, double eta, double* __restrict__ o1, double* __restrict__ o2,
+                                                      double* __restrict__ oq1, double* __restrict__ oq2,
+                                                      double* __restrict__ tv, int n, int m, int kt) {
+  constexpr int RPB = 256 / LG;
+  constexpr bool HP = MODE != 2;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s12[kBlkCols], s3[kBlkVec];
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c) s12[c] = 0.0;
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) s3[v] = 0.0;
+    if (j < n) {
+      const int e = t_rowptr[j + 1];
+      for (int k = t_rowptr[j] + l; k < e; k += LG) {
+        const double a = t_vals[k];
+        const int p = t_colind[k];
+        const f64x2* t = reinterpret_cast<const f64x2*>(y + (size_t)p * kBlkCols);
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v) {
+          const f64x2 u = t[v];
+          s12[2 * v] += a * u.x;
+          s12[2 * v + 1] += a * u.y;
+        }
+        if (HP) {
+          const f64x2* kp = reinterpret_cast<const f64x2*>(keep + (size_t)p * kBlkVec);
+#pragma unroll
+          for (int v = 0; v < kBlkVec / 2; ++v) {
+            const f64x2 u = kp[v];
+            s3[2 * v] += a * u.x;
+            s3[2 * v + 1] += a * u.y;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s12[c] += __shfl_xor(s12[c], o);
+    if (HP) {
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v)
+#pragma unroll
+        for (int o = LG / 2; o > 0; o >>= 1) s3[v] += __shfl_xor(s3[v], o);
+    }
+    if (l == 0 && j < n) {
+      const double qv = HP ? q[j] : 0.0;
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)j * kBlkCols + 2 * v);
+        const double s1 = s12[2 * v], s2 = s12[2 * v + 1];
+        if (MODE == 1) tv[(size_t)j * kBlkVec + v] = s1;
+        if (v < kt) {
+          if (HP) {
+            o1[(size_t)v * n + j] = (t.y - s2) - qv * s1 + 2.0 * sigma * s1 + rho * s3[v] + eta * t.x;
+          } else {
+            if (o1) o1[(size_t)v * n + j] = t.x - s1;
+            if (o2) o2[(size_t)v * n + j] = t.y - s2;
+          }
+        }
+      }
+    }
+  }
+  if (MODE == 2 && (oq1 || oq2)) {
+    const int64_t chunk = ((int64_t)m + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < m ? lo + chunk : m;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+      const size_t dst = (size_t)(rperm ? rperm[p] : p);
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        if (v < kt) {
+          const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * kBlkCols + 2 * v);
+          if (oq1) oq1[(size_t)v * m + dst] = t.x;
+          if (oq2) oq2[(size_t)v * m + dst] = t.y;
+        }
+      }
+    }
+  }
+}
+
+// out[v][j] -= (R tv[.][v])_j for the vectors of a tile, a lane group per row of R (tv: [n][kBlkVec], complete only after the
+// A' pass)
+template <int LG>
+__global__ __launch_bounds__(256) void k_bqb_rsub(const int32_t* __restrict__ r_rowptr, const int32_t* __restrict__ r_colind,
+                                                  const double* __restrict__ r_vals, const double* __restrict__ tv, double* out,
+                                                  int n, int kt) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s[kBlkVec];
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) s[v] = 0.0;
+    if (j < n) {
+      const int e = r_rowptr[j + 1];
+      for (int k = r_rowptr[j] + l; k < e; k += LG) {
+        const double a = r_vals[k];
+        const f64x2* t = reinterpret_cast<const f64x2*>(tv + (size_t)r_colind[k] * kBlkVec);
+#pragma unroll
+        for (int v = 0; v < kBlkVec / 2; ++v) {
+          const f64x2 u = t[v];
+          s[2 * v] += a * u.x;
+          s[2 * v + 1] += a * u.y;
+        }
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s[v] += __shfl_xor(s[v], o);
+    if (l == 0 && j < n) {
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v)
+        if (v < kt) out[(size_t)v * n + j] -= s[v];
+    }
+  }
+}
+
+}  // namespace fpsq

@@ -45,7 +45,7 @@ def _small():
 
 
 def _lanes(qp):
-    """lane_group(nnz(R), n) of csrc/fpsq_dense.hip"""
+    """lane_group(nnz(R), n) of csrc/fpsq_direct.hip.h"""
     mean = (int(qp.hess_vals.size) - int(np.count_nonzero(qp.hess_csr().diagonal()))) // qp.n
     lg = 1
     while lg < 64 and 2 * lg <= mean:

@@ -1,7 +1,7 @@
 // Developer probe (not part of the product): phase timing inside the 128 x 128 diagonal-block kernel of the direct
 // back-ends (k_potrf_inv128m), via s_memtime stamps of thread 0.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DFPSQ_POTRF_TIMING -I fletcherpenaltysolver.jl_amd/csrc -o tools/potrf_probe tools/potrf_probe.hip
-#include "fpsq_dense.hip.h"
+#include "fpsq_direct.hip.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
