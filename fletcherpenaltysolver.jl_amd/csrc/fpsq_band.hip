@@ -34,6 +34,15 @@ struct fpsq_band_s : DirectCore {
   double *blk_xg = nullptr, *blk_keep = nullptr, *blk_tv = nullptr;
   double* blk_stage[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool have_vals = false;    // a factorisation has put the Jacobian's values into vals / t_vals (fpsq_band_jac_mul, fpsq_band_qp_*)
+  // bordered band (fpsq_band_create_bordered; kernels and algebra: fpsq_band.hip.h "bordered band"): the last `border` stored
+  // rows are eliminated after the band of the first mb = m - border rows; nb, band_w, Mb and the sweeps describe that band
+  // alone, mpad pads m.  bd_c / bd_z: C and Z = B^-1 C, [mpad][16]; bd_l: the factor of S, [16][16]; bd_part: the partial
+  // sums of a correction, [bd_grid][256]; bd_t: the border's right-hand side while its slots receive w, [256]
+  int border = 0;
+  int64_t mb = 0;
+  double *bd_c = nullptr, *bd_z = nullptr, *bd_l = nullptr, *bd_part = nullptr, *bd_t = nullptr;
+  int bd_grid = 1;
+  hipEvent_t evS0 = nullptr, evS1 = nullptr;  // around the border's share of a factorisation (last_border_ms)
   fpsq_band_info info{};
 };
 
@@ -128,8 +137,8 @@ std::vector<int32_t> rcm_rows(int64_t m, int64_t n, const std::vector<int32_t>& 
 // the pattern, reorders the rows when that pays (rp / ci are replaced by the reordered structure; rperm_h / vperm_h map
 // stored rows / entries to the caller's, empty = identity) and decides on the two elimination chains.  Returns an error
 // text, empty on success.
-std::string band_order(int64_t n, int64_t m, std::vector<int32_t>& rp, std::vector<int32_t>& ci, std::vector<int32_t>& rperm_h,
-                       std::vector<int32_t>& vperm_h, int& chain_safe, int& chain_bw) {
+std::string band_order_rows(int64_t n, int64_t m, std::vector<int32_t>& rp, std::vector<int32_t>& ci,
+                            std::vector<int32_t>& rperm_h, std::vector<int32_t>& vperm_h, int& chain_safe, int& chain_bw) {
   const int64_t nnz = rp[m];
   chain_safe = chain_bw = 0;
   // validate, then the natural half bandwidth (rows): if the band is wide, try a reverse Cuthill-McKee ordering of the rows
@@ -218,12 +227,130 @@ std::string band_order(int64_t n, int64_t m, std::vector<int32_t>& rp, std::vect
   return std::string();
 }
 
+// half bandwidth of A A' in 128-row blocks over the first `rows` rows of a stored structure
+int64_t band_blocks(int64_t n, int64_t rows, const std::vector<int32_t>& rp, const std::vector<int32_t>& ci) {
+  std::vector<int32_t> lo(n, INT32_MAX), hi(n, -1);
+  for (int64_t i = 0; i < rows; ++i)
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
+      lo[ci[k]] = std::min(lo[ci[k]], (int32_t)(i / kDB));
+      hi[ci[k]] = std::max(hi[ci[k]], (int32_t)(i / kDB));
+    }
+  int64_t bwb = 0;
+  for (int64_t c = 0; c < n; ++c)
+    if (hi[c] >= 0) bwb = std::max<int64_t>(bwb, hi[c] - lo[c]);
+  return bwb;
+}
+
+// The ordering with a BORDER of at most max_border rows (include/fpsq.h, fpsq_band_create_bordered, has the rule): first the
+// ordering of all rows, as band_order_rows leaves it; then, candidates being the max_border rows of widest column span
+// (ties: the lower row first), the shortest prefix of them whose removal leaves rows that band_order_rows orders into a band
+// at most a quarter as wide (in blocks).  If there is one, those rows are stored last (ascending) behind that ordering of
+// the others and `border` counts them; else the result is the ordering of all rows and border = 0.
+std::string band_order(int64_t n, int64_t m, std::vector<int32_t>& rp, std::vector<int32_t>& ci, std::vector<int32_t>& rperm_h,
+                       std::vector<int32_t>& vperm_h, int& chain_safe, int& chain_bw, int max_border, int& border) {
+  border = 0;
+  std::vector<int32_t> rp0, ci0;
+  if (max_border > 0) {
+    rp0 = rp;
+    ci0 = ci;
+  }
+  const std::string msg = band_order_rows(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw);
+  if (!msg.empty() || max_border <= 0 || m < 2) return msg;
+  const int64_t bwb0 = band_blocks(n, m, rp, ci);
+  if (bwb0 == 0) return msg;
+  std::vector<int64_t> span(m, 0);
+  for (int64_t i = 0; i < m; ++i) {
+    int32_t lo = INT32_MAX, hi = -1;
+    for (int32_t k = rp0[i]; k < rp0[i + 1]; ++k) {
+      lo = std::min(lo, ci0[k]);
+      hi = std::max(hi, ci0[k]);
+    }
+    span[i] = hi >= 0 ? (int64_t)hi - lo + 1 : 0;
+  }
+  std::vector<int32_t> cand(m);
+  for (int64_t i = 0; i < m; ++i) cand[i] = (int32_t)i;
+  const int64_t ncand = std::min<int64_t>(max_border, m - 1);
+  std::partial_sort(cand.begin(), cand.begin() + ncand, cand.end(),
+                    [&](int32_t a, int32_t b) { return span[a] != span[b] ? span[a] > span[b] : a < b; });
+  std::vector<char> out(m, 0);
+  for (int64_t k = 1; k <= ncand; ++k) {
+    out[cand[k - 1]] = 1;
+    const int64_t mb = m - k;
+    std::vector<int32_t> rows_b, rp_b(1, 0), ci_b, ent_b;  // the other rows in the caller's order; ent_b: entry -> the caller's
+    rows_b.reserve(mb);
+    for (int64_t i = 0; i < m; ++i) {
+      if (out[i]) continue;
+      rows_b.push_back((int32_t)i);
+      for (int32_t t = rp0[i]; t < rp0[i + 1]; ++t) {
+        ci_b.push_back(ci0[t]);
+        ent_b.push_back(t);
+      }
+      rp_b.push_back((int32_t)ci_b.size());
+    }
+    ci_b.resize(std::max<size_t>(ci_b.size(), 1));
+    std::vector<int32_t> rperm_b, vperm_b;
+    int cs = 0, cb = 0;
+    if (!band_order_rows(n, mb, rp_b, ci_b, rperm_b, vperm_b, cs, cb).empty()) break;
+    if (4 * band_blocks(n, mb, rp_b, ci_b) > bwb0) continue;
+    // taken: the band rows as ordered, then the border rows
+    const int64_t nnz = rp0[m], nnz_b = rp_b[mb];
+    std::vector<int32_t> rp2(m + 1, 0), ci2(std::max<int64_t>(nnz, 1)), rr2(m), vp2(std::max<int64_t>(nnz, 1));
+    for (int64_t p = 0; p < mb; ++p) {
+      rr2[p] = rows_b[rperm_b.empty() ? p : rperm_b[p]];
+      rp2[p + 1] = rp_b[p + 1];
+    }
+    for (int64_t t = 0; t < nnz_b; ++t) {
+      ci2[t] = ci_b[t];
+      vp2[t] = ent_b[vperm_b.empty() ? t : vperm_b[t]];
+    }
+    int64_t p = mb;
+    for (int64_t i = 0; i < m; ++i) {
+      if (!out[i]) continue;
+      rr2[p] = (int32_t)i;
+      rp2[p + 1] = rp2[p] + (rp0[i + 1] - rp0[i]);
+      for (int32_t t = rp0[i], u = rp2[p]; t < rp0[i + 1]; ++t, ++u) {
+        ci2[u] = ci0[t];
+        vp2[u] = t;
+      }
+      ++p;
+    }
+    rp.swap(rp2);
+    ci.swap(ci2);
+    rperm_h.swap(rr2);
+    vperm_h.swap(vp2);
+    chain_safe = cs;
+    chain_bw = cb;
+    border = (int)k;
+    break;
+  }
+  return msg;
+}
+
 inline size_t blk_off(const fpsq_band b, int64_t i, int64_t j) {  // block (i, j), i - (band_w - 1) <= j <= i
   return ((size_t)i * b->band_w + (size_t)(j - i + b->band_w - 1)) * kDB * kDB;
 }
 
-// q (in b->r2, [mpad][2]) <- M^-1 r2 with the banded factor; result in b->r2
+// The correction of an M-solve on a bordered handle, behind the sweeps (y: b->r2 with NC = 2, b->r16 with NC = 16): rows < mb
+// hold B^-1 r, rows mb .. m - 1 still the border's right-hand side t; afterwards all of them hold M^-1 [r; t]
+template <int NC>
+void border_correct(fpsq_band b, double* y) {
+  hipLaunchKernelGGL(k_border_reduce<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_c, y, (int)b->mb, b->border,
+                     b->bd_part, b->bd_t);
+  hipLaunchKernelGGL(k_border_update<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_z, b->bd_l, b->bd_part, b->bd_grid,
+                     b->bd_t, y, (int)b->mb, b->border);
+}
+
+void band_sweeps(fpsq_band b);
+
+// q (in b->r2, [mpad][2]) <- M^-1 r2 with the banded factor (and the border's correction, whichever form the sweeps take);
+// result in b->r2
 void band_solve(fpsq_band b) {
+  band_sweeps(b);
+  if (b->border) border_correct<2>(b, b->r2);
+}
+
+// the sweeps on the band rows: b->r2 <- B^-1 b->r2 (rows beyond the band's blocks are not touched)
+void band_sweeps(fpsq_band b) {
   hipStream_t s = b->stream;
   const int nb = (int)b->nb, bw = b->band_w - 1;
   if (b->chain)  // (both elimination chains advance side by side inside the one launch)
@@ -292,14 +419,16 @@ struct BandSymbolic {
   std::vector<int32_t> rperm, vperm;  // stored row / entry -> the caller's (empty: identity)
   std::vector<int32_t> tptr, trow, tperm;  // the transposed structure (for P = rhs - A' Q) with the value permutation
   std::vector<int2> span;                  // {first, last column} of every row
-  int maxspan = 1, chain_safe = 0, chain_bw = 0;
-  int64_t bwb = 0;  // half bandwidth in blocks
+  int maxspan = 1, chain_safe = 0, chain_bw = 0;  // (maxspan: over the band rows)
+  int64_t bwb = 0;  // half bandwidth in blocks (of the band rows)
+  int border = 0;   // rows stored last and eliminated as a border
 };
 
 // Validate and order on the host (the role of ldl_analyze, src/solve_two_systems_struct.jl:344): the structure of
 // A A' + delta I is a band whose half width is the largest row distance of two entries of one column of A.  Reads the
 // caller's CSR (host or device memory); returns an error text, empty on success.
-std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, BandSymbolic& sy) {
+std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int max_border,
+                          BandSymbolic& sy) {
   std::vector<int32_t>&rp = sy.rp, &ci = sy.ci;
   rp.resize(m + 1);
   if (hipMemcpy(rp.data(), rowptr, (size_t)(m + 1) * 4, hipMemcpyDefault) != hipSuccess || rp[0] != 0)
@@ -308,8 +437,9 @@ std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int
   ci.resize(std::max<int64_t>(nnz, 1));
   if (nnz > 0 && (!colind || hipMemcpy(ci.data(), colind, (size_t)nnz * 4, hipMemcpyDefault) != hipSuccess))
     return "fpsq_band_create: cannot read colind";
-  const std::string msg = band_order(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw);
+  const std::string msg = band_order(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_border, sy.border);
   if (!msg.empty()) return msg;
+  const int64_t mb = m - sy.border;
   std::vector<int32_t> cfirst(n, INT32_MAX), clast(n, -1), seen(n, -1);
   std::vector<int32_t>& tcnt = sy.tptr;
   tcnt.assign(n + 1, 0);
@@ -323,13 +453,15 @@ std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int
       hi = std::max(hi, c);
       has_dup |= seen[c] == (int32_t)i;
       seen[c] = (int32_t)i;
-      cfirst[c] = std::min<int32_t>(cfirst[c], (int32_t)i);
-      clast[c] = std::max<int32_t>(clast[c], (int32_t)i);
+      if (i < mb) {
+        cfirst[c] = std::min<int32_t>(cfirst[c], (int32_t)i);
+        clast[c] = std::max<int32_t>(clast[c], (int32_t)i);
+      }
       tcnt[c + 1]++;
     }
     if (hi < 0) lo = hi = 0;
     sy.span[i] = int2{lo, hi};
-    sy.maxspan = std::max(sy.maxspan, hi - lo + 1);
+    if (i < mb) sy.maxspan = std::max(sy.maxspan, hi - lo + 1);
   }
   if (has_dup) return "fpsq_band_create: the CSR pattern has duplicate entries (sum them first)";
   for (int64_t c = 0; c < n; ++c)
@@ -420,6 +552,47 @@ void band_upload(fpsq_band b, const BandSymbolic& sy) {
   }
   hipDeviceSynchronize();
 }
+
+// The buffers of a bordered handle: the block sweeps' own (Z = B^-1 C is one tile of them) with the tile A multiplies, C, Z,
+// the factor of S, the partial sums and the saved right-hand side of a correction.  Non-zero (the handle is destroyed): failed.
+int border_setup(fpsq_band b) {
+  if (b->border == 0) return FPSQ_OK;
+  b->bd_grid = (int)std::max<int64_t>(1, std::min<int64_t>((b->mb + 255) / 256, kBorderGrid));
+  hipEventCreate(&b->evS0);
+  hipEventCreate(&b->evS1);
+  const size_t tile = (size_t)b->mpad * kBlkCols;
+  if (chain16_setup(b) || dalloc(b, &b->blk_xg, (size_t)b->n * kBlkCols) || dalloc(b, &b->bd_c, tile) ||
+      dalloc(b, &b->bd_z, tile) || dalloc(b, &b->bd_l, (size_t)kBorderMax * kBorderMax) ||
+      dalloc(b, &b->bd_part, (size_t)b->bd_grid * 256) || dalloc(b, &b->bd_t, 256)) {
+    g_band_create_error = b->err;
+    fpsq_band_destroy(b);
+    return FPSQ_ERR_HIP;
+  }
+  return FPSQ_OK;
+}
+
+// The border's share of a factorisation, behind the band's Cholesky on b->stream: [C; D] = A A_s' by the block A product on
+// the scattered border rows, Z = B^-1 C by the 16-column sweeps, S = D + delta I - C'Z and its Cholesky
+void border_factor(fpsq_band b, double delta) {
+  hipStream_t s = b->stream;
+  const int mb = (int)b->mb;
+  const size_t tile = (size_t)b->mpad * kBlkCols * 8;
+  hipEventRecord(b->evS0, s);
+  hipMemsetAsync(b->blk_xg, 0, (size_t)b->n * kBlkCols * 8, s);
+  hipLaunchKernelGGL(k_border_scatter, dim3(b->border), dim3(256), 0, s, b->rowptr, b->colind, b->vals, mb, b->blk_xg);
+  const int lgA = lane_group(b->nnz, b->m);
+  WITH_LANE_GROUP(lgA, hipLaunchKernelGGL(k_bqb_prologue<LG>, dim3((unsigned)std::min<int64_t>(
+                                              (b->mpad + 256 / lgA - 1) / (256 / lgA), 2048)), dim3(256), 0, s, b->rowptr,
+                                          b->colind, b->vals, b->blk_xg, b->r16, (double*)nullptr, (int)b->m, (int)b->mpad))
+  hipMemcpyAsync(b->bd_c, b->r16, tile, hipMemcpyDeviceToDevice, s);
+  chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
+  hipMemcpyAsync(b->bd_z, b->r16, tile, hipMemcpyDeviceToDevice, s);
+  hipLaunchKernelGGL(k_border_reduce<kBlkCols>, dim3(b->bd_grid), dim3(256), 0, s, b->bd_c, b->bd_z, mb, b->border, b->bd_part,
+                     b->bd_t);
+  hipLaunchKernelGGL(k_border_chol, dim3(1), dim3(256), 0, s, b->bd_part, b->bd_grid, b->bd_c, mb, b->border, delta, b->piv_tol,
+                     b->piv_reg, b->bd_l, b->info_dev);
+  hipEventRecord(b->evS1, s);
+}
 }  // namespace
 
 extern "C" {
@@ -428,6 +601,15 @@ const char* fpsq_band_last_error(fpsq_band b) { return b ? b->err.c_str() : g_ba
 
 int fpsq_band_analyze(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t* row_perm,
                       fpsq_band_info* info) {
+  return fpsq_band_analyze_bordered(n, m, rowptr, colind, 0, row_perm, info);
+}
+
+int fpsq_band_analyze_bordered(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border,
+                               int32_t* row_perm, fpsq_band_info* info) {
+  if (max_border < 0 || max_border > kBorderMax) {
+    g_band_create_error = "fpsq_band_analyze: max_border must be 0 .. 16";
+    return FPSQ_ERR_ARG;
+  }
   if (n <= 0 || m <= 0 || !rowptr || n >= INT32_MAX || m >= INT32_MAX - 256 || rowptr[0] != 0) {
     g_band_create_error = "fpsq_band_analyze: bad arguments (0-based CSR in HOST memory expected)";
     return FPSQ_ERR_ARG;
@@ -445,8 +627,8 @@ int fpsq_band_analyze(int64_t n, int64_t m, const int32_t* rowptr, const int32_t
   }
   std::vector<int32_t> ci(colind, colind + nnz), rperm_h, vperm_h;
   ci.resize(std::max<int64_t>(nnz, 1));
-  int chain_safe = 0, chain_bw = 0;
-  const std::string msg = band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw);
+  int chain_safe = 0, chain_bw = 0, border = 0;
+  const std::string msg = band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, border);
   if (!msg.empty()) {
     g_band_create_error = msg;
     return FPSQ_ERR_ARG;
@@ -454,17 +636,9 @@ int fpsq_band_analyze(int64_t n, int64_t m, const int32_t* rowptr, const int32_t
   if (row_perm)
     for (int64_t p = 0; p < m; ++p) row_perm[p] = rperm_h.empty() ? (int32_t)p : rperm_h[p];
   if (info) {
-    std::vector<int32_t> lo(n, INT32_MAX), hi(n, -1);
-    for (int64_t i = 0; i < m; ++i)
-      for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
-        lo[ci[k]] = std::min(lo[ci[k]], (int32_t)(i / kDB));
-        hi[ci[k]] = std::max(hi[ci[k]], (int32_t)(i / kDB));
-      }
-    int64_t bwb = 0;
-    for (int64_t c = 0; c < n; ++c)
-      if (hi[c] >= 0) bwb = std::max<int64_t>(bwb, hi[c] - lo[c]);
-    const int64_t nb = (m + kDB - 1) / kDB;
-    bwb = std::min(bwb, nb - 1);
+    const int64_t mb = m - border;
+    const int64_t nb = (mb + kDB - 1) / kDB;
+    const int64_t bwb = std::min(band_blocks(n, mb, rp, ci), nb - 1);
     *info = fpsq_band_info{};
     info->n = n;
     info->m = m;
@@ -474,6 +648,7 @@ int fpsq_band_analyze(int64_t n, int64_t m, const int32_t* rowptr, const int32_t
     info->factor_bytes = nb * (bwb + 1) * (int64_t)kDB * kDB * 8;
     info->reordered = rperm_h.empty() ? 0 : 1;
     info->chains = chain_safe > 0 ? 2 : 1;
+    info->border_rows = border;
   }
   return FPSQ_OK;
 }
@@ -483,6 +658,8 @@ int fpsq_band_destroy(fpsq_band b) {
   core_teardown(b);
   if (b->evA) hipEventDestroy(b->evA);
   if (b->evB) hipEventDestroy(b->evB);
+  if (b->evS0) hipEventDestroy(b->evS0);
+  if (b->evS1) hipEventDestroy(b->evS1);
   if (b->stream2) {
     hipStreamSynchronize(b->stream2);
     hipStreamDestroy(b->stream2);
@@ -492,6 +669,15 @@ int fpsq_band_destroy(fpsq_band b) {
 }
 
 int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t device) {
+  return fpsq_band_create_bordered(out, n, m, rowptr, colind, 0, device);
+}
+
+int fpsq_band_create_bordered(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind,
+                              int32_t max_border, int32_t device) {
+  if (max_border < 0 || max_border > kBorderMax) {
+    g_band_create_error = "fpsq_band_create: max_border must be 0 .. 16";
+    return FPSQ_ERR_ARG;
+  }
   if (!out || n <= 0 || m <= 0 || !rowptr || n >= INT32_MAX || m >= INT32_MAX - 256) {
     g_band_create_error = "fpsq_band_create: bad arguments";
     return FPSQ_ERR_ARG;
@@ -508,7 +694,7 @@ int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr
     return FPSQ_ERR_HIP;
   }
   BandSymbolic sy;
-  const std::string msg = band_symbolic(n, m, rowptr, colind, sy);
+  const std::string msg = band_symbolic(n, m, rowptr, colind, max_border, sy);
   if (!msg.empty()) {
     g_band_create_error = msg;
     return FPSQ_ERR_ARG;
@@ -519,8 +705,10 @@ int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr
   b->m = m;
   b->nnz = sy.rp[m];
   b->device = device;
+  b->border = sy.border;
+  b->mb = m - sy.border;
   b->mpad = (m + kDB - 1) / kDB * kDB;
-  b->nb = b->mpad / kDB;
+  b->nb = (b->mb + kDB - 1) / kDB;  // (the blocks of the band rows; = mpad / 128 without a border)
   b->band_w = (int)std::min<int64_t>(sy.bwb, b->nb - 1) + 1;
   b->span = sy.maxspan;
   b->chain_safe = sy.chain_safe;
@@ -530,6 +718,10 @@ int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr
   if (int rc = band_choose_form(b)) return rc;
   if (int rc = band_alloc(b)) return rc;
   band_upload(b, sy);
+  if (int rc = border_setup(b)) {
+    *out = nullptr;
+    return rc;
+  }
   hipFuncSetAttribute((const void*)k_potrf_inv128m, hipFuncAttributeMaxDynamicSharedMemorySize, kPotrfLds5);
   hipFuncSetAttribute((const void*)k_gemm128_lds<0>, hipFuncAttributeMaxDynamicSharedMemorySize, kG128Lds0);
   hipFuncSetAttribute((const void*)k_gemm128_lds<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kG128Lds1);
@@ -546,12 +738,22 @@ int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr
   b->info.reordered = b->reordered ? 1 : 0;
   b->info.chains = b->chain_safe > 0 ? 2 : 1;
   b->info.factor_bytes = (int64_t)band_factor_bytes(b);
+  b->info.border_rows = b->border;
   *out = b;
   return FPSQ_OK;
 }
 
 int fpsq_band_create_coo(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
                          int32_t index_base, int32_t device) {
+  return fpsq_band_create_coo_bordered(out, n, m, nnz, rows, cols, index_base, 0, device);
+}
+
+int fpsq_band_create_coo_bordered(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
+                                  int32_t index_base, int32_t max_border, int32_t device) {
+  if (max_border < 0 || max_border > kBorderMax) {
+    g_band_create_error = "fpsq_band_create_coo: max_border must be 0 .. 16";
+    return FPSQ_ERR_ARG;
+  }
   if (!out || n <= 0 || m <= 0 || nnz < 0 || nnz >= INT32_MAX || (nnz > 0 && (!rows || !cols))) {
     g_band_create_error = "fpsq_band_create_coo: bad arguments";
     return FPSQ_ERR_ARG;
@@ -576,7 +778,7 @@ int fpsq_band_create_coo(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, cons
   std::vector<int32_t> rp(m + 1, 0);
   for (int64_t i = 0; i < ns; ++i) rp[srow[i] + 1]++;
   for (int64_t i = 0; i < m; ++i) rp[i + 1] += rp[i];
-  if (int rc = fpsq_band_create(out, n, m, rp.data(), scol.data(), device)) return rc;
+  if (int rc = fpsq_band_create_bordered(out, n, m, rp.data(), scol.data(), max_border, device)) return rc;
   fpsq_band b = *out;
   const bool dup = ns != nnz;
   if (dalloc(b, &b->coo_perm, (size_t)std::max<int64_t>(nnz, 1)) || dalloc(b, &b->coo_in, (size_t)std::max<int64_t>(nnz, 1)) ||
@@ -632,10 +834,10 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
   // numeric phase 1: M = A A' + delta I into the band (jac_coord! + sparse(...) of src/solve_linear_system.jl:223-233)
   if (b->form_gen == 1)
     hipLaunchKernelGGL(k_band_form, dim3(nb), dim3(256), (size_t)b->span * 16, s, b->rowptr, b->colind, b->vals, b->rowspan,
-                       (int)b->m, (int)b->mpad, W, delta, b->Mb, b->span);
+                       (int)b->mb, nb * kDB, W, delta, b->Mb, b->span);
   else
     hipLaunchKernelGGL(k_band_form_t, dim3(nb), dim3(256), (size_t)b->form_R * W * kDB * 8, s, b->rowptr, b->colind, b->vals,
-                       b->t_rowptr, b->t_colind, b->t_vals, (int)b->m, (int)b->mpad, W, delta, b->Mb, b->form_R);
+                       b->t_rowptr, b->t_colind, b->t_vals, (int)b->mb, nb * kDB, W, delta, b->Mb, b->form_R);
   hipEventRecord(b->e1, s);
   // numeric phase 2: right-looking block-banded Cholesky (ldl_factorize!, :234), the dense back-end's block kernels.
   // One step: diagonal block k, panel blocks (k + st j, k) and trailing blocks (k + st i, k + st j), 1 <= j <= i <= rem
@@ -668,8 +870,26 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
     k0 = 2 * b->chain_safe;
   }
   for (int k = k0; k < nb; ++k) step(s, k, 1, std::min(bw, nb - 1 - k));
+  if (b->border) border_factor(b, delta);
   int32_t pivot = 0;
   const int rc = factor_end(b, &b->info.last_form_ms, &b->info.last_chol_ms, &b->info.regularized_pivots, &pivot);
+  if (b->border) {
+    // the sweeps that formed Z may have raised the error word: it is looked at and cleared HERE, whatever the code above, so
+    // that it never surfaces as the time-out of a later, unrelated solve
+    const bool expired = *b->chain_err != 0;
+    *b->chain_err = 0;
+    if (rc >= 0) {
+      float ms = 0.f;
+      hipEventElapsedTime(&ms, b->evS0, b->evS1);
+      b->info.last_border_ms = ms;
+      b->info.last_chol_ms -= ms;  // (the band's Cholesky alone, as on a handle without a border)
+      if (expired) {
+        b->factored = false;
+        b->err = "band_factorize: Z = B^-1 C did not arrive (bounded wait of the block sweep expired)";
+        return FPSQ_ERR_TIMEOUT;
+      }
+    }
+  }
   if (rc >= 0 && info)  // (first non-positive pivot, 1-based, in the CALLER's row numbering)
     *info = pivot > 0 && b->reordered && pivot <= (int32_t)b->m ? b->rperm_host[pivot - 1] + 1 : pivot;
   return rc;
@@ -1000,6 +1220,7 @@ void blk_solve_tile(fpsq_band b, int lgA, double* keep) {
   WITH_LANE_GROUP(lgA, hipLaunchKernelGGL(k_bqb_prologue<LG>, dim3(bq_grid(b->mpad, lgA)), dim3(256), 0, b->stream, b->rowptr,
                                           b->colind, b->vals, b->blk_xg, b->r16, keep, (int)b->m, (int)b->mpad))
   chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
+  if (b->border) border_correct<kBlkCols>(b, b->r16);
 }
 }  // namespace
 

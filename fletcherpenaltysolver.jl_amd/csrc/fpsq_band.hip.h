@@ -755,4 +755,148 @@ __global__ __launch_bounds__(256) void k_bqb_rsub(const int32_t* __restrict__ r_
   }
 }
 
+// ---- bordered band (fpsq_band_create_bordered): the s <= kBorderMax rows of A stored LAST couple with every row of M,
+//   M = [B C; C' D],  B = A_b A_b' + delta I (mb x mb, the band the sweeps factor),  C = A_b A_s',  D = A_s A_s' + delta I.
+// A factorisation keeps C and Z = B^-1 C as [.][16] arrays (columns >= s zero) and the Cholesky factor of S = D - C'Z; an
+// M-solve is the sweeps on the band rows, which leave y = B^-1 r in rows < mb and the border's right-hand side t untouched
+// in rows mb .. mb + s - 1 (the sweeps pass over rows >= mb at most as padding rows of the last block: identity pivots, zero
+// couplings), followed by k_border_reduce and k_border_update:  w = S^-1 (t - C'y),  u = y - Z w.
+// NC = interleaved right-hand-side columns of the sweeps' array (2: k_trsv_chain / k_trsv_step3, 16: k_trsm_chain16).  Every
+// sum has a fixed order that depends on the shape alone (rows in index order inside a workgroup's slice, slices and then
+// workgroups in index order, the 16 border columns in index order), column c reads column c only: a column's bits depend
+// neither on its position, nor on its neighbours, nor on how many there are.  No atomics, no waits.
+constexpr int kBorderMax = 16;
+constexpr int kBorderGrid = 128;  // most workgroups of the two kernels (every update workgroup re-sums all the partials)
+
+// part[blk][i][c] = sum over this workgroup's band rows p of C[p][i] y[p][c];  workgroup 0 also saves t (tsave[i][c] =
+// y[mb + i][c], zero for i >= s), which k_border_update overwrites with w
+template <int NC>
+__global__ __launch_bounds__(256) void k_border_reduce(const double* __restrict__ Cm, const double* __restrict__ y, int mb,
+                                                       int s, double* __restrict__ part, double* __restrict__ tsave) {
+  constexpr int NO = kBorderMax * NC;  // sums of a workgroup
+  constexpr int NS = 256 / NO;         // row slices: thread = (slice, sum)
+  __shared__ double sh[256];
+  const int o = threadIdx.x % NO, sl = threadIdx.x / NO, i = o / NC, c = o % NC;
+  const int chunk = (mb + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int lo = min(mb, (int)blockIdx.x * chunk), hi = min(mb, lo + chunk);
+  double a = 0.0;
+  for (int p = lo + sl; p < hi; p += NS) a += Cm[(size_t)p * kBorderMax + i] * y[(size_t)p * NC + c];
+  if (NS > 1) {
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    if (sl == 0)
+      for (int q = 1; q < NS; ++q) a += sh[q * NO + o];
+  }
+  if (sl == 0) {
+    part[(size_t)blockIdx.x * NO + o] = a;
+    if (blockIdx.x == 0) tsave[o] = i < s ? y[(size_t)(mb + i) * NC + c] : 0.0;
+  }
+}
+
+// every workgroup: g = t - sum of the partials (index order), w = L'^-1 L^-1 g (one thread per column), then its own slice
+// of the band rows, y[p][c] -= sum_i Z[p][i] w[i][c]; workgroup 0 writes w into the border rows.  Ls: the factor of S,
+// [16][16] row-major, lower, identity beyond s.
+template <int NC>
+__global__ __launch_bounds__(256) void k_border_update(const double* __restrict__ Zm, const double* __restrict__ Ls,
+                                                       const double* __restrict__ part, int nparts,
+                                                       const double* __restrict__ tsave, double* y, int mb, int s) {
+  constexpr int NO = kBorderMax * NC;
+  __shared__ double L[kBorderMax * kBorderMax];
+  __shared__ double g[NO];
+  L[threadIdx.x] = Ls[threadIdx.x];
+  if (threadIdx.x < NO) {
+    double a = 0.0;
+    for (int q = 0; q < nparts; ++q) a += part[(size_t)q * NO + threadIdx.x];
+    g[threadIdx.x] = tsave[threadIdx.x] - a;
+  }
+  __syncthreads();
+  if (threadIdx.x < NC) {
+    const int c = threadIdx.x;
+    double w[kBorderMax];
+#pragma unroll
+    for (int i = 0; i < kBorderMax; ++i) {
+      double v = g[i * NC + c];
+#pragma unroll
+      for (int k = 0; k < i; ++k) v -= L[i * kBorderMax + k] * w[k];
+      w[i] = v / L[i * kBorderMax + i];
+    }
+#pragma unroll
+    for (int i = kBorderMax - 1; i >= 0; --i) {
+      double v = w[i];
+#pragma unroll
+      for (int k = i + 1; k < kBorderMax; ++k) v -= L[k * kBorderMax + i] * w[k];
+      w[i] = v / L[i * kBorderMax + i];
+    }
+#pragma unroll
+    for (int i = 0; i < kBorderMax; ++i) g[i * NC + c] = w[i];
+  }
+  __syncthreads();
+  const int chunk = (mb + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int lo = min(mb, (int)blockIdx.x * chunk), hi = min(mb, lo + chunk);
+  for (int64_t idx = (int64_t)lo * NC + threadIdx.x; idx < (int64_t)hi * NC; idx += 256) {
+    const int64_t p = idx / NC;
+    const int c = (int)(idx % NC);
+    const double* z = Zm + (size_t)p * kBorderMax;
+    double a = 0.0;
+#pragma unroll
+    for (int i = 0; i < kBorderMax; ++i) a += z[i] * g[i * NC + c];
+    y[idx] -= a;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < NO && (int)threadIdx.x / NC < s)
+    y[(size_t)mb * NC + threadIdx.x] = g[threadIdx.x];  // (row mb + i, column c: i * NC + c behind row mb)
+}
+
+// xg[colind[k]][i] = vals[k] over the entries of border row i (stored row mb + i): A_s' as the interleaved [n][16] tile the
+// block A product multiplies (the tile is zeroed first; a row holds a column once)
+__global__ __launch_bounds__(256) void k_border_scatter(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                        const double* __restrict__ vals, int mb, double* __restrict__ xg) {
+  const int i = blockIdx.x;
+  for (int k = rowptr[mb + i] + threadIdx.x; k < rowptr[mb + i + 1]; k += 256) xg[(size_t)colind[k] * kBlkCols + i] = vals[k];
+}
+
+// One workgroup: S = D + delta I - C'Z from the partials of C'Z (k_border_reduce<16> on Z, summed in index order) and the
+// rows mb .. mb + s - 1 of CD = A A_s' (lower triangle), then its Cholesky factor into Ls ([16][16], identity beyond s).
+// Pivots by the rule of wave_diag16: one that is not above tol (0 when no regularisation is set) is replaced by reg (1 when
+// none is set) and counted in info[1] resp. reported in info[0] (first one wins) as stored row mb + j, 1-based.
+__global__ __launch_bounds__(256) void k_border_chol(const double* __restrict__ part, int nparts, const double* __restrict__ CD,
+                                                     int mb, int s, double delta, double tol, double reg,
+                                                     double* __restrict__ Ls, int* info) {
+  __shared__ double S[kBorderMax][kBorderMax + 1];
+  const int i = threadIdx.x / kBorderMax, j = threadIdx.x % kBorderMax;
+  {
+    double a = 0.0;
+    for (int q = 0; q < nparts; ++q) a += part[(size_t)q * 256 + threadIdx.x];
+    double v = i == j ? 1.0 : 0.0;
+    if (i < s && j < s) v = (CD[(size_t)(mb + i) * kBorderMax + j] + (i == j ? delta : 0.0)) - a;
+    S[i][j] = v;
+  }
+  __syncthreads();
+  const bool dyn = reg > 0.0;
+  const double thr = dyn ? tol : 0.0, sub = dyn ? reg : 1.0;
+  int nbad = 0, first = 0;
+  for (int k = 0; k < s; ++k) {
+    if (threadIdx.x == 0) {
+      double d = S[k][k];
+      if (!(d > thr)) {
+        first = nbad == 0 ? k + 1 : first;
+        ++nbad;
+        d = sub;
+      }
+      S[k][k] = sqrt(d);
+    }
+    __syncthreads();
+    if (j == k && i > k) S[i][k] /= S[k][k];
+    __syncthreads();
+    if (j > k && i >= j) S[i][j] -= S[i][k] * S[j][k];
+    __syncthreads();
+  }
+  Ls[threadIdx.x] = j <= i ? S[i][j] : 0.0;
+  if (threadIdx.x == 0 && nbad) {
+    if (dyn)
+      atomicAdd(info + 1, nbad);
+    else
+      atomicCAS(info, 0, mb + first);
+  }
+}
+
 }  // namespace fpsq

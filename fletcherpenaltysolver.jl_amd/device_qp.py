@@ -175,7 +175,10 @@ class DeviceBandEqQP:
     `problems.with_sparse_hessian`) is evaluated with that Hessian (`fpsq_band_qp_create_csr`).  The factor is rebuilt lazily -- once, at the next evaluation -- after
     `set_delta` or `set_jacobian_values`; `info()["factorizations"]` counts how many this object has run.
     ldlt_tol / ldlt_r2: the dynamic regularisation of `LDLtSolver`, defaults as in qdsolver._DirectQDSolver (sqrt(eps),
-    -sqrt(eps); "drop" drops a vanishing pivot).  Has the surface `fps_solve_device` uses on DeviceEqQP."""
+    -sqrt(eps); "drop" drops a vanishing pivot).  Has the surface `fps_solve_device` uses on DeviceEqQP.
+    `border` (class attribute, 0 .. 16; DeviceBorderedBandEqQP sets it per object): the max_border the handle is created with."""
+
+    border = 0
 
     def __init__(self, qp, sigma=1e3, rho=1.0, delta=0.0, eta=0.0, device=0, ldlt_tol=None, ldlt_r2=None):
         from .qdsolver import _ldlt_r2
@@ -187,7 +190,8 @@ class DeviceBandEqQP:
         rp = np.ascontiguousarray(qp.rowptr, dtype=np.int32)
         ci = np.ascontiguousarray(qp.colind, dtype=np.int32)
         h = C.c_void_p()
-        if self._lib.fpsq_band_create(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, self.device) != 0:
+        if self._lib.fpsq_band_create_bordered(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, int(self.border),
+                                               self.device) != 0:
             raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
         self._h = h
         try:
@@ -344,6 +348,18 @@ class DeviceBandEqQP:
             self.close()
         except Exception:
             pass
+
+
+class DeviceBorderedBandEqQP(DeviceBandEqQP):
+    """DeviceBandEqQP on a BORDERED band: at most `border` (0 .. 16) long constraint rows -- rows that couple with every other
+    row of M = A A' + delta I, such as a mean-value, volume or mass-conservation constraint or the wrap-around rows of a
+    periodic boundary -- are eliminated last instead of widening the band (include/fpsq.h "BORDERED BAND").  Every method
+    is the base class's; `info()["border_rows"]` says how many rows were taken (0: the handle is DeviceBandEqQP's).  The
+    other keywords are DeviceBandEqQP's (whose parameter list stays as it is)."""
+
+    def __init__(self, qp, border=16, **kwargs):
+        self.border = int(border)
+        super().__init__(qp, **kwargs)
 
 
 def rccl_unique_id() -> bytes:

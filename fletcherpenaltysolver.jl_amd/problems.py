@@ -124,6 +124,43 @@ def with_sparse_hessian(qp: EqQP, half_width: int = 2, seed: int = 4321) -> EqQP
                                hess_colind=Q.indices.astype(np.int32), hess_vals=Q.data.astype(np.float64))
 
 
+def with_border_rows(qp: EqQP, s: int, kind: str = "mean", seed: int = 0) -> EqQP:
+    """A copy of `qp` with `s` LONG constraint rows appended (rows m .. m + s - 1) and `b` extended by A xhat on them, so
+    xhat stays feasible.  Long rows couple with every other row of A A': the case of the bordered band
+    (include/fpsq.h "BORDERED BAND").
+      kind = "mean":     row r touches every 16th column, r % 16, r % 16 + 16, ... -- a weighted mean over a stride of the
+                         variables; values (0.5 + u(seed, entry, 31)) / sqrt(entries of the row), entry = r * n + column.
+      kind = "periodic": row r couples the FIRST and the LAST columns, 4 r .. 4 r + 3 and n - 1 - (4 r .. 4 r + 3) -- the
+                         wrap-around rows of a periodic boundary; values 2 u(seed, entry, 32) - 1, + 2 on the first (needs
+                         n >= 8 s)."""
+    s = int(s)
+    assert s >= 1
+    n = qp.n
+    cols, vals = [], []
+    for r in range(s):
+        if kind == "mean":
+            c = np.arange(r % 16, n, 16, dtype=np.int64)
+            v = (0.5 + uniform01(seed, r * n + c, 31)) / np.sqrt(c.size)
+        elif kind == "periodic":
+            assert n >= 8 * s
+            k = 4 * r + np.arange(4, dtype=np.int64)
+            c = np.concatenate([k, (n - 1 - k)[::-1]])
+            v = 2.0 * uniform01(seed, r * n + c, 32) - 1.0
+            v[0] += 2.0
+        else:
+            raise ValueError(f"kind must be 'mean' or 'periodic', not {kind!r}")
+        cols.append(c)
+        vals.append(v)
+    counts = np.array([c.size for c in cols], dtype=np.int64)
+    cols, vals = np.concatenate(cols), np.concatenate(vals)
+    rowptr = np.concatenate([qp.rowptr.astype(np.int64), qp.rowptr[-1] + np.cumsum(counts)])
+    b_new = np.array([np.dot(vals[lo:hi], qp.xhat[cols[lo:hi]])
+                      for lo, hi in zip(np.cumsum(counts) - counts, np.cumsum(counts))])
+    return dataclasses.replace(qp, name=f"{qp.name}+{s}{kind}", m=qp.m + s, rowptr=rowptr.astype(np.int32),
+                               colind=np.concatenate([qp.colind, cols]).astype(np.int32),
+                               vals=np.concatenate([qp.vals, vals]), b=np.concatenate([qp.b, b_new]))
+
+
 def _stratified_rows(m, n, per_row, start, width, seed, diag_col=None, diag_boost=0.0):
     """Each of the m rows gets `per_row` sorted, distinct columns: one per stratum of
     [start[i], start[i] + width).  If diag_col is given, the stratum containing diag_col[i] is

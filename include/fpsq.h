@@ -338,7 +338,26 @@ int fpsq_dense_get_info(fpsq_dense d, fpsq_dense_info *info);
  *   fpsq_band_solve_two_*  = `ldiv!` with two right-hand sides (:189-203, :236-251) on the cached factor.
  * Storage is (m / 128) x (half bandwidth in blocks + 1) blocks; create fails with FPSQ_ERR_STATE when that does not fit
  * the device (or the half bandwidth exceeds 143 blocks AND a row spans more than 9600 columns), with FPSQ_ERR_ARG when
- * the pattern holds duplicate entries.  Arguments may be host or device pointers; calls are synchronous. */
+ * the pattern holds duplicate entries.  Arguments may be host or device pointers; calls are synchronous.
+ *
+ * BORDERED BAND (fpsq_band_create_bordered, _create_coo_bordered, _analyze_bordered: the entries above plus max_border, 0 ..
+ * 16, anything else FPSQ_ERR_ARG; the entries above ARE these with max_border = 0).  A few constraint rows that touch columns
+ * all over the range -- a mean-value, volume or mass-conservation constraint, the wrap-around rows of a periodic boundary --
+ * couple with every row of M, and no ordering narrows such a band.  Up to max_border of them are eliminated LAST instead: in
+ * the stored order (band rows first, the s border rows last)
+ *     M = [B C; C' D],   B = A_b A_b' + delta I (the band that is factored),   C = A_b A_s',   D = A_s A_s' + delta I,
+ * a factorisation also forms Z = B^-1 C (one tile of the block sweeps) and the s x s Cholesky of S = D - C'Z, and every
+ * M-solve of every entry below is  y = B^-1 r (the sweeps),  w = S^-1 (t - C'y),  u = y - Z w  (two launches more).
+ * SELECTION, deterministic: the candidates are the max_border rows of widest column span (last - first column + 1; ties: the
+ * lower row index first), taken widest first; the border is the SHORTEST such prefix after whose removal the remaining rows,
+ * put through the ordering described above (reverse Cuthill-McKee when wide, then the two-ended order), have a half
+ * bandwidth in blocks of at most a quarter of the half bandwidth the ordering of ALL rows gives.  No such prefix (more long
+ * rows than max_border, or nothing to gain): the border is empty and the handle is the one max_border = 0 gives, bit for
+ * bit.  Border rows are stored last, in ascending order of the caller's index; fpsq_band_analyze_bordered lists them at the
+ * end of row_perm.  nblocks, bandwidth_blocks, factor_bytes and chains describe the band part.  The dynamic regularisation
+ * applies to the pivots of S by the rule of the pivots of B; without it a non-positive pivot of S gives the soft code 1 with
+ * *info = that border row (1-based, the caller's numbering), and regularized_pivots counts the pivots of S too.  All sums
+ * of the correction have a fixed order: calls are repeatable and the block entries keep their DETERMINISM contract. */
 typedef struct fpsq_band_s *fpsq_band;
 typedef struct {
   int64_t n, m, nnz;
@@ -350,20 +369,28 @@ typedef struct {
   int64_t reordered;         /* 1: the symbolic phase reordered the rows of A (reverse Cuthill-McKee and / or the two-ended
                                 order of the two elimination chains) */
   int64_t chains;            /* 2: the band is eliminated from both ends at once (two streams), 1: one chain */
+  int64_t border_rows;       /* rows eliminated last as a border (0 unless created with max_border > 0 and rows were taken) */
+  double last_border_ms;     /* device time of C, D, Z, S and its Cholesky in the last factorisation (not in last_chol_ms) */
 } fpsq_band_info;
 int fpsq_band_create(fpsq_band *out, int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind, int32_t device);
+int fpsq_band_create_bordered(fpsq_band *out, int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind,
+                              int32_t max_border, int32_t device);
 /* The same from the model's COO structure (`jac_structure!`, struct.jl:331-337; index_base 1 for Julia; duplicates allowed
  * and summed) -- with fpsq_band_factorize_coo taking the output of `jac_coord!` (nnz values in that order, HOST or DEVICE
  * memory): the sorted order is kept on the device and one gather(-sum) kernel fills the CSR slots, so neither the caller nor
  * the binding re-orders anything per x (src/solve_linear_system.jl:223-234). */
 int fpsq_band_create_coo(fpsq_band *out, int64_t n, int64_t m, int64_t nnz, const int64_t *rows, const int64_t *cols,
                          int32_t index_base, int32_t device);
+int fpsq_band_create_coo_bordered(fpsq_band *out, int64_t n, int64_t m, int64_t nnz, const int64_t *rows, const int64_t *cols,
+                                  int32_t index_base, int32_t max_border, int32_t device);
 int fpsq_band_factorize_coo(fpsq_band b, const double *vals, double delta, int32_t *info);
 /* the ordering decisions of fpsq_band_create alone, on the host (no device needed; rowptr / colind in HOST memory): row_perm
  * (m entries, may be null) = the caller's row stored at each position, info = blocks / half bandwidth / factor bytes /
  * reordered / chains of the structure fpsq_band_create would set up. */
 int fpsq_band_analyze(int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind, int32_t *row_perm,
                       fpsq_band_info *info);
+int fpsq_band_analyze_bordered(int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind, int32_t max_border,
+                               int32_t *row_perm, fpsq_band_info *info);
 int fpsq_band_destroy(fpsq_band b);
 const char *fpsq_band_last_error(fpsq_band b);
 int fpsq_band_set_regularization(fpsq_band b, double tol, double reg);
