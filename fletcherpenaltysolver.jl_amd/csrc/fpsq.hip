@@ -862,6 +862,8 @@ struct fpsq_solver_s {
   LaneCtl* ctl_mp;              // constant {-1, 1}
   LaneCtl* ctl_m0;              // constant {-1, 0}: p2 = -A'q2 (two_mixed_device)
   bool craig_x = false;         // FPSQ_CRAIG_X=1: CRAIG carries x through its loop (the recurrence xs += e0 v~) instead of p2 = xsign A'q2 behind it
+  int tail_lanes = 3;           // FPSQ_TAIL_LANES=2: fpsq_solve_two_mixed / fpsq_ys_gs form v = -A'q2 and p1 = g - A'q1 by a single-lane product
+                                // launch each, not as two lanes of ONE launch (k_spmv_seam)
   bool craig_v_alone = false;   // FPSQ_CRAIG_X=2 (tests): no recurrence, and p2 ALWAYS by the single-lane product k_spmv<1, ..>, never inside a tail launch
   Comm* comm = nullptr;         // null: single GPU
   // Halo mode of the sharded handle (fpsq_comm_set_halo): n is the length of this rank's COLUMN WINDOW; its first
@@ -1861,6 +1863,17 @@ bool launch_at_tail(fpsq_handle h, const double* x, double* yout, const GradEpi&
   h->spmv_launches++;
   h->prod_at[NL - 1]++;
   return true;
+}
+
+// p1 = g - A'q1 and v = vsign A'q2 of two plain vectors in ONE launch (k_spmv_seam): what fpsq_solve_two_mixed and fpsq_ys_gs
+// hand out behind the recurrences, bitwise the two single-lane products (at_product_const) it stands for
+void launch_at_seam(fpsq_handle h, const double* q1, const double* g, double* p1, const double* q2, double vsign, double* v,
+                    Gates gates = {}) {
+  const DevCsr& M = h->AT;
+  launch_product(h, k_spmv_seam, dim3((M.nblk + 7) / 8 * 8), M.view(), q1, q2, g, p1, vsign, v, gates.c0, gates.c1);
+  h->launches++;
+  h->spmv_launches++;
+  h->prod_at[1]++;
 }
 
 __global__ void k_set_ctl(LaneCtl* c, double ca, double cb) {
@@ -3825,7 +3838,13 @@ int two_mixed_device(fpsq_handle h, const double* g, double* c, bool defer_p1 = 
   lanes[1].y = h->Cy;
   lanes[1].st = &h->hstats[1];
   // p1 = rhs1 - Aop' q1                                                   :126-127
+  // (neither deferred -- fpsq_solve_two_mixed, fpsq_ys_gs, an evaluation with rho = 0 -- and column-sorted padded A' blocks: the two share ONE stream of the matrix)
+  const bool seam = x_from_y && !defer_p2 && !defer_p1 && h->tail_lanes == 3 && !h->craig_v_alone && h->AT.sorted && h->AT.padded;
   TailFn full = [&](const TailCtx& t) -> int {
+    if (seam) {
+      launch_at_seam(h, h->Lx[0], g, h->p1, h->Cy, lanes[1].xsign, h->Cx, t.gates);
+      return tail ? (*tail)(t) : 0;
+    }
     if (x_from_y && !defer_p2)
       if (int rc = at_product_const(h, lanes[1].xsign, h->Cy, 0.0, nullptr, h->Cx, t.gates)) return rc;
     if (!defer_p1)
@@ -3997,6 +4016,7 @@ int fpsq_create(fpsq_handle* out, int64_t n, int64_t m, const fpsq_options* opts
     if (const char* at = std::getenv("FPSQ_FUSE_PROBE_AT")) h->fuse_probe_at = std::atoll(at);
   }
   if (const char* ev = std::getenv("FPSQ_FUSE_TAIL")) h->fuse_tail = std::atoi(ev) != 0;
+  if (const char* ev = std::getenv("FPSQ_TAIL_LANES")) h->tail_lanes = std::atoi(ev) == 2 ? 2 : 3;
   if (const char* ev = std::getenv("FPSQ_CRAIG_X")) {
     h->craig_x = std::atoi(ev) == 1;
     h->craig_v_alone = std::atoi(ev) == 2;

@@ -172,8 +172,8 @@ __device__ __forceinline__ void csort_fetch(const CsrView& A, int L, int cbase, 
 // (FPSQ_FUSE_TAIL=0).  With GradEpi::y2 the third product of the tail, v = vsign A'y2, shares the launch: the block's entries are
 // in registers anyway, so the workgroup gathers y2 for them as well, parks those products in the (single-lane) head of the product
 // buffer, sums its rows exactly as k_spmv<1, ..> does, and only then stages the two-lane products -- 0.8 MB of gathers and one more
-// trip through LDS instead of another stream of the matrix; the buffer stays at 32 KB (three lanes side by side: 48 KB, three
-// workgroups per CU instead of four).
+// trip through LDS instead of another stream of the matrix; the buffer stays at 32 KB (three lanes side by side -- 48 KB, three
+// workgroups per CU instead of four -- took 41.0 us against 39.6: profiles/tail_three_lanes.md).
 // VRAW (FPSQ_FUSE_TAIL=0 on such a handle: NL = 2, not GRAD): the plain raw product -- rows written by row_epilogue as ever, for
 // k_qp_penalty_grad -- with the same single-lane pass for v ahead of it, so that the two-launch tail stays two launches.  A template
 // parameter: the one-launch tail's kernel carries none of it.
@@ -436,6 +436,76 @@ __global__ __launch_bounds__(kBlock) void k_spmv(CsrView A, const double* __rest
     if (tid == 0) {
 #pragma unroll
       for (int l = 0; l < NL; ++l) partials[(size_t)l * pstride + L] = sq[l];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ p1 and v in one launch
+//
+// What fpsq_solve_two_mixed / fpsq_ys_gs hand out behind the two recurrences on one GPU (column-sorted padded blocks):
+//   p1 = g - A'q1   and   v = vsign A'q2,
+// two PLAIN vectors gathered side by side -- q1 and q2 are not interleaved, nor are the results -- in ONE stream of the matrix
+// where two launches of k_spmv<1, ..> make two.  The products of both lanes go to k_spmv<2, ..>'s pair buffer [slot][2] (32 KB),
+// into the slots they have there, and phase 2 adds them in row_segment_sum's order -- which does not depend on the lane count
+// -- so each row is BITWISE the row of the single-lane kernel; the row epilogues are row_epilogue's with (ca, cb) = (-1, 1) and
+// (vsign, 0), whose products are exact however the compiler contracts them.
+__global__ __launch_bounds__(kBlock) void k_spmv_seam(CsrView A, const double* __restrict__ q1, const double* __restrict__ q2,
+                                                      const double* g, double* p1, double vsign, double* vout,
+                                                      const LaneCtl* gate0, const LaneCtl* gate1) {
+  constexpr int kPer = kSpmvNnz / kBlock;
+  __shared__ double prod[kSpmvNnz * 2];
+  // speculatively enqueued: runs only once both recurrences of the call have ended
+  if (gate0 != nullptr && !(gate0->done && gate1->done)) return;
+  const int L = (int)blockIdx.x;
+  if (L >= A.nblk) return;
+  const int tid = threadIdx.x;
+  const bool shared = A.segdesc != nullptr;  // (kernel-uniform)
+  uint4 sw16;
+  uint2 sw8;
+  int r0, nr, s, cbase;
+  int cidx[kPer], slot[kPer];
+  double v[kPer];
+  if (shared) {  // the block's head through the scalar cache, value loads issued first (cshared_head)
+    cshared_head(A, L, tid, sw16, sw8, r0, nr, s, cbase, v);
+  } else {
+    const int4 bd = A.blkdesc[L];
+    cbase = A.colbase[L];
+    r0 = bd.x, nr = bd.y, s = bd.z;
+  }
+  int G = 1;
+  while (G < 64 && G * 2 * nr <= kBlock) G <<= 1;
+  const int rows_per_pass = kBlock / G;
+  const int g_ = tid / G, gl = tid % G;
+  const int rq0 = g_ < nr ? g_ : 0;
+  const int seg_a0 = A.rowptr[r0 + rq0], seg_b0 = A.rowptr[r0 + rq0 + 1];
+  const double gpre = g[r0 + rq0];  // the epilogue's operand of the first row pass, requested ahead of the gathers
+  if (shared) cshared_decode(sw16, sw8, cbase, cidx, slot);
+  else csort_fetch(A, L, cbase, tid, cidx, slot, v);
+  double xa[kPer], xb[kPer];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) xa[k] = q1[cidx[k]];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) xb[k] = q2[cidx[k]];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) *reinterpret_cast<double2*>(prod + 2 * slot[k]) = make_double2(v[k] * xa[k], v[k] * xb[k]);
+  lds_barrier();
+  // phase 2: G lanes per row
+  for (int base = 0; base < nr; base += rows_per_pass) {
+    const int rr = base + g_;
+    const bool valid = rr < nr;
+    double acc[2] = {0.0, 0.0};
+    if (valid) {
+      const int a = (base == 0 ? seg_a0 : A.rowptr[r0 + rr]) - s, b = (base == 0 ? seg_b0 : A.rowptr[r0 + rr + 1]) - s;
+      row_segment_sum<2>(prod, a + gl, b, G, acc);
+    }
+    for (int off = G >> 1; off > 0; off >>= 1) {
+      acc[0] += __shfl_down(acc[0], off, 64);
+      acc[1] += __shfl_down(acc[1], off, 64);
+    }
+    if (valid && gl == 0) {
+      const int64_t row = r0 + rr;
+      p1[row] = (base == 0 ? gpre : g[row]) - acc[0];  // (ca = -1, cb = 1)
+      vout[row] = vsign * acc[1] + 0.0;                // (ca = vsign, cb = 0: ca acc + 0)
     }
   }
 }
