@@ -838,7 +838,7 @@ struct fpsq_solver_s {
   bool fuse_halo_ok = false;
   bool fuse_halo_on = true;               // FPSQ_FUSE_HALO=0: a handle with shared rows keeps the halo launch between two product launches
   std::vector<int32_t> fz_rb;
-  std::vector<int2> fz_colrange;
+  std::vector<Range2> fz_colrange;
   unsigned int* fz_flag = nullptr;        // per A' block: launch number of its last completion
   unsigned long long* fz_ptag = nullptr;  // per A' block: four tagged words (its squared-norm partials)
   unsigned long long* ride_rec2 = nullptr;  // the mid leaders' record
@@ -991,491 +991,105 @@ inline int ew_grid(int64_t n) {
 }
 
 // ------------------------------------------------------------------ host-side sparse set-up
+// Every stored layout is BUILT by fpsq_layout.h (plain host code, checked on the CPU by tests/host/layout_check.cpp); what
+// follows uploads what the builders return, one function per layout.
 
-struct HostCsr {
-  int64_t nrows, ncols;
-  std::vector<int32_t> rowptr, colind;
-};
+static_assert(sizeof(BlkDesc) == sizeof(int4) && sizeof(SegDesc) == sizeof(uint4) && sizeof(Range2) == sizeof(int2),
+              "fpsq_layout.h: host images of the descriptor arrays the kernels read as int4 / uint4 / int2");
+static_assert(sizeof(RgcsGroup) == 32, "two 16-byte loads at the head of a row group's workgroup");
 
-// align > 1 (the A' blocks of a handle whose iterations run as one launch, k_iter_fused): a block that holds at least `align` rows
-// ends on a multiple of `align` rows -- with 16-byte rows of the long pair and align = 8 every 128-byte line of the product's
-// output then belongs to ONE block.  (Blocks of fewer rows -- very long rows -- stay as they are: rowblocks_aligned() says so.)
-std::vector<int32_t> make_rowblocks(const std::vector<int32_t>& rowptr, int64_t nrows, int align = 1) {
-  std::vector<int32_t> rb;
-  rb.push_back(0);
-  int64_t r = 0;
-  while (r < nrows) {
-    int64_t r1 = r;
-    int64_t nz = 0;
-    while (r1 < nrows && (r1 - r) < kMaxRowsPerBlk) {
-      const int64_t len = rowptr[r1 + 1] - rowptr[r1];
-      if (nz + len > kSpmvNnz) break;
-      nz += len;
-      ++r1;
-    }
-    if (r1 == r) r1 = r + 1;  // a single row longer than kSpmvNnz gets a block of its own
-    else if (align > 1 && r1 < nrows && r1 - r >= align) r1 = r + (r1 - r) / align * align;
-    rb.push_back((int32_t)r1);
-    r = r1;
-  }
-  return rb;
+template <class T>
+int upload(fpsq_handle h, T* dst, const std::vector<T>& src) {
+  if (!src.empty()) HIPCHK(h, hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return 0;
+}
+template <class T>
+int dalloc_upload(fpsq_handle h, T** p, const std::vector<T>& src) {
+  if (int rc = dalloc(h, p, src.size())) return rc;
+  return upload(h, *p, src);
 }
 
-bool rowblocks_aligned(const std::vector<int32_t>& rb, int align) {
-  for (size_t i = 0; i + 1 < rb.size(); ++i)
-    if (rb[i] % align) return false;
-  return true;
-}
-
-// transpose structure: returns CSR of A' and perm with AT slot t <- A slot perm[t]
-void transpose_structure(const HostCsr& A, HostCsr& T, std::vector<int32_t>& perm) {
-  const int64_t nnz = (int64_t)A.colind.size();
-  T.nrows = A.ncols;
-  T.ncols = A.nrows;
-  T.rowptr.assign(T.nrows + 1, 0);
-  for (int64_t k = 0; k < nnz; ++k) T.rowptr[A.colind[k] + 1]++;
-  for (int64_t j = 0; j < T.nrows; ++j) T.rowptr[j + 1] += T.rowptr[j];
-  T.colind.resize(nnz);
-  perm.resize(nnz);
-  std::vector<int32_t> next(T.rowptr.begin(), T.rowptr.end() - 1);
-  for (int64_t i = 0; i < A.nrows; ++i)
-    for (int32_t k = A.rowptr[i]; k < A.rowptr[i + 1]; ++k) {
-      const int32_t t = next[A.colind[k]]++;
-      T.colind[t] = (int32_t)i;
-      perm[t] = k;
-    }
-}
-
-int upload_csr(fpsq_handle h, const HostCsr& H, DevCsr& D) {
+int upload_blocks(fpsq_handle h, const HostCsr& H, const BlockLayout& B, DevCsr& D) {
   D.nrows = H.nrows;
   D.ncols = H.ncols;
   D.nnz = (int64_t)H.colind.size();
   D.nstore = D.nnz;
-  std::vector<int32_t> rb = make_rowblocks(H.rowptr, H.nrows, D.row_align);
-  D.nblk = (int32_t)rb.size() - 1;
+  D.nblk = B.nblk();
   if (int rc = dalloc(h, &D.rowptr, H.rowptr.size())) return rc;
   // one padding entry (column 0, value 0): the product kernels read index `s` of an empty row block unconditionally
   if (int rc = dalloc(h, &D.colind, H.colind.size() + 1)) return rc;
   if (int rc = dalloc(h, &D.vals, H.colind.size() + 1)) return rc;
   HIPCHK(h, hipMemset(D.colind + H.colind.size(), 0, 4));
   HIPCHK(h, hipMemset(D.vals + H.colind.size(), 0, 8));
-  if (int rc = dalloc(h, &D.rowblk, rb.size())) return rc;
-  HIPCHK(h, hipMemcpy(D.rowptr, H.rowptr.data(), H.rowptr.size() * 4, hipMemcpyHostToDevice));
-  if (!H.colind.empty())
-    HIPCHK(h, hipMemcpy(D.colind, H.colind.data(), H.colind.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(D.rowblk, rb.data(), rb.size() * 4, hipMemcpyHostToDevice));
-  {
-    std::vector<int4> bd(std::max(D.nblk, 1));
-    for (int b = 0; b < D.nblk; ++b) bd[b] = int4{rb[b], rb[b + 1] - rb[b], H.rowptr[rb[b]], H.rowptr[rb[b + 1]]};
-    if (int rc = dalloc(h, &D.blkdesc, bd.size())) return rc;
-    HIPCHK(h, hipMemcpy(D.blkdesc, bd.data(), bd.size() * sizeof(int4), hipMemcpyHostToDevice));
-  }
-  // 16-bit block-relative columns when every row block spans < 65536 columns
-  if (h->opt.jac_format != 1 && D.nnz > 0) {
-    std::vector<int32_t> base(D.nblk, 0);
-    std::vector<uint16_t> c16(D.nnz + 1, 0);
-    bool ok = true;
-    int span = 0;
-    for (int b = 0; b < D.nblk && ok; ++b) {
-      const int s = H.rowptr[rb[b]], e = H.rowptr[rb[b + 1]];
-      int lo = INT32_MAX, hi = -1;
-      for (int k = s; k < e; ++k) {
-        lo = std::min(lo, H.colind[k]);
-        hi = std::max(hi, H.colind[k]);
-      }
-      if (e == s) lo = hi = 0;
-      if (hi - lo > 65535) ok = false;
-      span = std::max(span, hi - lo + 1);
-      base[b] = lo;
-      for (int k = s; k < e && ok; ++k) c16[k] = (uint16_t)(H.colind[k] - lo);
-    }
-    if (ok) {
-      if (int rc = dalloc(h, &D.col16, c16.size())) return rc;
-      if (int rc = dalloc(h, &D.colbase, base.size())) return rc;
-      HIPCHK(h, hipMemcpy(D.col16, c16.data(), c16.size() * 2, hipMemcpyHostToDevice));
-      HIPCHK(h, hipMemcpy(D.colbase, base.data(), base.size() * 4, hipMemcpyHostToDevice));
-      D.win = span;
-    }
+  if (int rc = dalloc(h, &D.rowblk, B.rb.size())) return rc;
+  if (int rc = upload(h, D.rowptr, H.rowptr)) return rc;
+  if (int rc = upload(h, D.colind, H.colind)) return rc;
+  if (int rc = upload(h, D.rowblk, B.rb)) return rc;
+  if (int rc = dalloc(h, &D.blkdesc, B.blkdesc.size())) return rc;
+  HIPCHK(h, hipMemcpy(D.blkdesc, B.blkdesc.data(), B.blkdesc.size() * sizeof(int4), hipMemcpyHostToDevice));
+  if (B.has_col16) {
+    if (int rc = dalloc_upload(h, &D.col16, B.col16)) return rc;
+    if (int rc = dalloc_upload(h, &D.colbase, B.colbase)) return rc;
+    D.win = B.win;
   }
   return 0;
 }
 
-// Re-store an uploaded CSR in the padded block layout of k_spmv<.., PAD>.  `perm` (value source of every compact entry)
-// is rewritten to the padded numbering with -1 in the padding slots.  No-op when some block is one long row.
-// csr_pos (optional, A' only): for every CSR slot of A its position in the padded row-group copy of A (build_rgcs), and
-// zero_pos, a position of that array that always holds 0.0.  When given -- and the blocks qualify for the column-sorted
-// layout -- the blocks are stored WITHOUT VALUES: an A' block's entries come from the ~10 row groups whose column windows
-// reach its columns, and inside a group (column-sorted) they are a contiguous run; the block's entries are therefore
-// stored in the order of their POSITIONS in the row-group array, 64 consecutive entries (one wave instruction) read at most
-// four runs, and one 16-byte descriptor per such segment says where: four 24-bit bases relative to the block's base
-// (blkdesc.w), three split lanes, the number of valid lanes.  The index planes keep the column-sorted format (slot in the
-// block's row-major order | column relative to colbase), so the products land in the same LDS slots and are summed in the
-// same order: BITWISE the other layouts.  What it buys: the Krylov loop streams ONE copy of the values (80 MB less
-// working set next to a 256 MB Infinity Cache: measured as a what-if in round 3, +3.9 % evaluations/s at the headline
-// size), a Jacobian refresh writes one array instead of two, 82 MB less memory.  The value addresses need the descriptors
-// first -- but so do the gathers of x need the index words, and values and gathers then travel in the same round trip: the
-// workgroup's chain of dependent memory round trips is no longer.
-int pad_blocks(fpsq_handle h, const HostCsr& H, std::vector<int32_t>& perm, DevCsr& D,
-               const std::vector<int32_t>* csr_pos = nullptr, int64_t zero_pos = 0, const double* ext_vals = nullptr) {
-  if (D.nnz == 0 || h->opt.jac_format == 1) return 0;
-  std::vector<int32_t> rb = make_rowblocks(H.rowptr, H.nrows, D.row_align);
-  const int nblk = (int)rb.size() - 1;
-  for (int b = 0; b < nblk; ++b)
-    if (H.rowptr[rb[b + 1]] - H.rowptr[rb[b]] > kSpmvNnz) return 0;
-  const size_t slots = (size_t)nblk * kSpmvNnz;
-  if (slots >= (size_t)INT32_MAX) return 0;
-  std::vector<int32_t> pperm(slots, -1), pcol;
-  std::vector<uint16_t> pc16;
-  std::vector<uint8_t> pc8;
-  std::vector<int32_t> base, ord;
-  const bool idx16 = D.col16 != nullptr;
-  // column-sorted blocks (k_spmv<.., CSORT>): 13 bits of block-relative column next to the 11-bit slot
-  const bool sorted = idx16 && D.win <= 8192 && h->at_sorted;
-  static_assert(kSpmvNnz <= 2048, "slot field of the column-sorted layout is 11 bits");
-  if (sorted) {
-    pc16.resize(slots);
-    for (size_t q = 0; q < slots; ++q) {  // padding: an unused slot (its own sorted position), column 0, value 0
-      const size_t t = q % kSpmvNnz;
-      pc16[q - t + 8 * ((t % 512) / 2) + 2 * (t / 512) + (t & 1)] = (uint16_t)t;
-    }
-    pc8.assign(slots, 0);
-    base.resize(nblk);
-    HIPCHK(h, hipMemcpy(base.data(), D.colbase, (size_t)nblk * 4, hipMemcpyDeviceToHost));
-  } else if (idx16) {
-    pc16.assign(slots, 0);
-    base.resize(nblk);
-    HIPCHK(h, hipMemcpy(base.data(), D.colbase, (size_t)nblk * 4, hipMemcpyDeviceToHost));
+// Re-store uploaded blocks in the padded layout pad_blocks() built (k_spmv<.., PAD>; nothing to do when it declined).
+// ext_vals / zero_pos (shared values): the row-group array of A the blocks read, and its entry that always holds 0.0.
+int upload_padded(fpsq_handle h, const PaddedLayout& P, DevCsr& D, const double* ext_vals, int64_t zero_pos) {
+  if (P.kind == PadKind::none) return 0;
+  const bool shared = P.kind == PadKind::shared;
+  // shared: what a refresh still has to fill is the side array of the blocks that keep their own values (+ 1: its padding)
+  const size_t nvals = shared ? (size_t)P.nown * kSpmvNnz + 1 : P.slots;
+  dfree(h, &D.vals);
+  dfree(h, &D.col16);
+  dfree(h, &D.colind);
+  if (int rc = dalloc(h, &D.vals, nvals)) return rc;
+  HIPCHK(h, hipMemset(D.vals, 0, nvals * 8));
+  if (P.kind == PadKind::pad32) {
+    if (int rc = dalloc_upload(h, &D.colind, P.col32)) return rc;
+  } else if (P.kind == PadKind::pad16) {  // the 16-bit form is the only one the padded kernel reads
+    if (int rc = dalloc_upload(h, &D.col16, P.c16)) return rc;
   } else {
-    pcol.assign(slots, 0);
-  }
-  // ---- shared values.  A block whose entries cannot be described that way (a 64-entry segment touching more than four
-  // runs: the first blocks of the headline generators, where the clamped windows of the top rows pile several groups' last
-  // few columns into one block) keeps 2048 values of its OWN in a small side array (D.vals, refreshed like before); its
-  // blkdesc.w = -128 - (its index there) tells the kernel.  More than a quarter of the blocks like that: not worth it.
-  bool shared = sorted && csr_pos != nullptr && h->at_shared && zero_pos < (int64_t)INT32_MAX;
-  std::vector<uint4> segd;
-  std::vector<int32_t> vbase, own_perm;
-  std::vector<uint16_t> sc16;
-  std::vector<uint8_t> sc8;
-  int nown = 0;
-  if (shared) {
-    segd.assign((size_t)nblk * 32, uint4{0u, 0u, 0u, 0u});
-    vbase.assign(nblk, 0);
-    sc16.resize(slots);
-    sc8.assign(slots, 0);
-    std::vector<int64_t> pos;
-    std::vector<uint4> sd(32);
-    for (int b = 0; b < nblk; ++b) {
-      const int s = H.rowptr[rb[b]], e = H.rowptr[rb[b + 1]], cnt = e - s;
-      ord.resize(cnt);
-      pos.resize(cnt);
-      for (int k = 0; k < cnt; ++k) {
-        ord[k] = k;
-        pos[k] = (*csr_pos)[perm[s + k]];
-      }
-      std::sort(ord.begin(), ord.end(), [&](int a, int c) { return pos[a] < pos[c]; });
-      const int64_t base64 = (cnt ? pos[ord[0]] : 0) - 64;
-      bool ok = true;
-      for (int sg = 0; sg < 32 && ok; ++sg) {
-        const int lo = sg * 64, nvalid = std::max(0, std::min(64, cnt - lo));
-        int64_t vb[4] = {0, 0, 0, 0};
-        int split[3] = {64, 64, 64};
-        int np = 0;
-        for (int l = 0; l < nvalid && ok; ++l) {
-          const int64_t p = pos[ord[lo + l]];
-          if (l == 0 || p != pos[ord[lo + l - 1]] + 1) {  // a new run starts at lane l
-            if (np == 4) {
-              ok = false;
-              break;
-            }
-            if (np > 0) split[np - 1] = l;
-            vb[np++] = p - l - base64;
-          }
-        }
-        for (int i = 0; i < 4; ++i)
-          if (vb[i] < 0 || vb[i] >= (1ll << 24)) ok = false;
-        const uint64_t a0 = (uint64_t)vb[0] | ((uint64_t)vb[1] << 24) | ((uint64_t)vb[2] << 48);
-        uint4 d;
-        d.x = (uint32_t)a0;
-        d.y = (uint32_t)(a0 >> 32);
-        d.z = (uint32_t)(((uint64_t)vb[2] >> 16) | ((uint64_t)vb[3] << 8));
-        d.w = (uint32_t)split[0] | ((uint32_t)split[1] << 7) | ((uint32_t)split[2] << 14) | ((uint32_t)nvalid << 21);
-        sd[(sg % 4) * 8 + sg / 4] = d;  // (stored per wave: segment 4 j + w at [8 w + j], a wave's eight in one 128-byte line)
-      }
-      if (ok) {
-        vbase[b] = (int32_t)base64;
-        for (int sg = 0; sg < 32; ++sg) segd[(size_t)b * 32 + sg] = sd[sg];
-      } else {  // its own values, in column-sorted order
-        vbase[b] = -128 - nown;
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int c) { return H.colind[s + a] < H.colind[s + c]; });
-        own_perm.resize((size_t)(nown + 1) * kSpmvNnz, -1);
-        for (int t = 0; t < cnt; ++t) own_perm[(size_t)nown * kSpmvNnz + t] = perm[s + ord[t]];
-        ++nown;
-      }
-      for (int t = 0; t < kSpmvNnz; ++t) {  // entry t of the stored order belongs to thread t % 256, its j-th word (j = t / 256)
-        const size_t qi = (size_t)b * kSpmvNnz + 8 * (t % kBlock) + t / kBlock;
-        if (t < cnt) {
-          const int k = ord[t], col = H.colind[s + k] - base[b];
-          sc16[qi] = (uint16_t)(k | ((col & 31) << 11));
-          sc8[qi] = (uint8_t)(col >> 5);
-        } else {
-          sc16[qi] = (uint16_t)t;  // an unused slot of the product buffer; its value is 0 (zero_pos / the side array's padding)
-        }
-      }
-    }
-    if (std::getenv("FPSQ_VERBOSE")) std::fprintf(stderr, "fpsq: shared A' values: %d of %d blocks keep their own\n", nown, nblk);
-    if (nown > nblk / 4) shared = false;
-  }
-  if (shared) {
-    dfree(h, &D.vals);
-    dfree(h, &D.col16);
-    dfree(h, &D.colind);
-    const size_t nown_slots = (size_t)nown * kSpmvNnz;
-    if (int rc = dalloc(h, &D.vals, nown_slots + 1)) return rc;
-    HIPCHK(h, hipMemset(D.vals, 0, (nown_slots + 1) * 8));
-    if (int rc = dalloc(h, &D.cs16, slots)) return rc;
-    if (int rc = dalloc(h, &D.cs8, slots)) return rc;
-    if (int rc = dalloc(h, &D.segdesc, segd.size())) return rc;
-    HIPCHK(h, hipMemcpy(D.cs16, sc16.data(), slots * 2, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(D.cs8, sc8.data(), slots, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(D.segdesc, segd.data(), segd.size() * sizeof(uint4), hipMemcpyHostToDevice));
-    std::vector<int4> bd(nblk);
-    for (int b = 0; b < nblk; ++b) bd[b] = int4{rb[b], rb[b + 1] - rb[b], H.rowptr[rb[b]], vbase[b]};
-    HIPCHK(h, hipMemcpy(D.blkdesc, bd.data(), bd.size() * sizeof(int4), hipMemcpyHostToDevice));
+    if (int rc = dalloc_upload(h, &D.cs16, P.c16)) return rc;
+    if (int rc = dalloc_upload(h, &D.cs8, P.c8)) return rc;
     D.sorted = true;
+  }
+  if (shared) {
+    if (int rc = dalloc(h, &D.segdesc, P.segdesc.size())) return rc;
+    HIPCHK(h, hipMemcpy(D.segdesc, P.segdesc.data(), P.segdesc.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(D.blkdesc, P.blkdesc.data(), P.blkdesc.size() * sizeof(int4), hipMemcpyHostToDevice));
     D.shared = true;
     D.vals_ext = ext_vals;
     D.zero_pos = zero_pos;
-    D.padded = true;
-    D.nstore = (int64_t)nown_slots;  // (what a refresh still has to fill: the side array)
-    perm.swap(own_perm);
-    return 0;
-  }
-  for (int b = 0; b < nblk; ++b) {
-    const int s = H.rowptr[rb[b]], e = H.rowptr[rb[b + 1]];
-    if (sorted) {
-      ord.resize(e - s);
-      for (int k = s; k < e; ++k) ord[k - s] = k;
-      std::stable_sort(ord.begin(), ord.end(), [&](int a, int c) { return H.colind[a] < H.colind[c]; });
-      for (int t = 0; t < e - s; ++t) {
-        const int k = ord[t], col = H.colind[k] - base[b];
-        const size_t q = (size_t)b * kSpmvNnz + t;
-        pperm[q] = perm[k];
-        // (index planes: the eight entries of a thread contiguously, see csort_fetch)
-        const size_t qi = (size_t)b * kSpmvNnz + 8 * ((t % 512) / 2) + 2 * (t / 512) + (t & 1);
-        pc16[qi] = (uint16_t)((k - s) | ((col & 31) << 11));
-        pc8[qi] = (uint8_t)(col >> 5);
-      }
-      continue;
-    }
-    for (int k = s; k < e; ++k) {
-      const size_t q = (size_t)b * kSpmvNnz + (k - s);
-      pperm[q] = perm[k];
-      if (idx16) pc16[q] = (uint16_t)(H.colind[k] - base[b]);
-      else pcol[q] = H.colind[k];
-    }
-  }
-  dfree(h, &D.vals);
-  if (int rc = dalloc(h, &D.vals, slots)) return rc;
-  HIPCHK(h, hipMemset(D.vals, 0, slots * 8));
-  if (sorted) {
-    dfree(h, &D.col16);
-    dfree(h, &D.colind);
-    if (int rc = dalloc(h, &D.cs16, slots)) return rc;
-    if (int rc = dalloc(h, &D.cs8, slots)) return rc;
-    HIPCHK(h, hipMemcpy(D.cs16, pc16.data(), slots * 2, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(D.cs8, pc8.data(), slots, hipMemcpyHostToDevice));
-    D.sorted = true;
-  } else if (idx16) {
-    dfree(h, &D.col16);
-    dfree(h, &D.colind);  // the 16-bit form is the only one the padded kernel reads
-    if (int rc = dalloc(h, &D.col16, slots)) return rc;
-    HIPCHK(h, hipMemcpy(D.col16, pc16.data(), slots * 2, hipMemcpyHostToDevice));
-  } else {
-    dfree(h, &D.colind);
-    if (int rc = dalloc(h, &D.colind, slots)) return rc;
-    HIPCHK(h, hipMemcpy(D.colind, pcol.data(), slots * 4, hipMemcpyHostToDevice));
   }
   D.padded = true;
-  D.nstore = (int64_t)slots;
-  perm.swap(pperm);
+  D.nstore = shared ? (int64_t)P.nown * kSpmvNnz : (int64_t)P.slots;
   return 0;
 }
 
-// Row-group column-sorted copy of A (see k_spmv_rgcs).  Not built (ok = false) when a group spans >= 2^21 columns.
-int build_rgcs(fpsq_handle h, const HostCsr& H, DevRgcs& D, std::vector<int32_t>* csr_pos = nullptr,
-               std::vector<int2>* col_range = nullptr) {
-  const int64_t nnz = (int64_t)H.colind.size();
+// Row-group column-sorted copy of A (k_spmv_rgcs): one padding entry behind the index words and the values
+int upload_rgcs(fpsq_handle h, const HostCsr& H, const RgcsLayout& L, DevRgcs& D) {
   D.ok = false;
-  if (csr_pos) csr_pos->clear();
-  if (nnz == 0 || h->opt.jac_format == 1) return 0;
-  std::vector<RgcsGroup> groups;
-  std::vector<uint32_t> pidx(nnz);
-  std::vector<int32_t> vperm(nnz);
-  std::vector<uint16_t> tptr;
-  std::vector<int32_t> ord, lrow, cntr, nxt;
-  // Nonzero budget of a group = a whole number of tiles (a workgroup pays the same latency for a partly filled
-  // tile), chosen so that the groups fill the GPU's resident-workgroup slots (4 per CU at 32 KB of LDS) about once:
-  // measured at the headline size, 1000 groups of 5 tiles run the product in ~30 us, 782 groups of 6.2 tiles in 37 us.
-  int budget = kRgcsGroupNnz;
-  {
-    hipDeviceProp_t prop;
-    int cus = 256;
-    if (hipGetDeviceProperties(&prop, h->opt.device) == hipSuccess && prop.multiProcessorCount > 0)
-      cus = prop.multiProcessorCount;
-    const int64_t slots = (int64_t)cus * 4;
-    const double avg = (double)nnz / (double)std::max<int64_t>(H.nrows, 1);
-    const int64_t kmax = std::max<int64_t>(1, (int64_t)(std::min<double>(kRgcsMaxRows * avg, kRgcsGroupNnz) / kRgcsTile));
-    const int64_t k = std::min(kmax, std::max<int64_t>(1, (nnz + slots * kRgcsTile - 1) / (slots * kRgcsTile)));
-    budget = (int)(k * kRgcsTile);
-    if (const char* ev = std::getenv("FPSQ_RGCS_TILES"))  // tuning override: tiles per group
-      budget = (int)(std::max<int64_t>(1, std::min<int64_t>(kmax, std::atoi(ev))) * kRgcsTile);
-  }
-  auto group_end = [&](int64_t r) {
-    int64_t r1 = r, nz = 0;
-    while (r1 < H.nrows && r1 - r < kRgcsMaxRows) {
-      const int64_t len = H.rowptr[r1 + 1] - H.rowptr[r1];
-      if (nz + len > budget && r1 > r) break;
-      nz += len;
-      ++r1;
-    }
-    return r1;
-  };
-  // ORDER OF THE ENTRIES INSIDE A GROUP: by column PHASE, (col mod P), P = the typical width of a group's column window.
-  // A workgroup sweeps its window tile by tile while all the groups of an XCD are resident together.  Sorted by column proper,
-  // group g reads column c when its sweep gets there -- (c - cmin_g) / width of the way through the launch -- and the ~9
-  // neighbouring groups whose windows overlap in c (PDE-like rows: the window moves by a fraction of its width from group to
-  // group) read it at nine different times, spread over the whole launch, while the matrix streams through the same L2:
-  // the x window was fetched 2.6 times (profiles/r03_pmc_traffic.json: 1.15 x the product's algorithmic bytes).  Sorted by
-  // phase every group is at the same ABSOLUTE columns at the same time -- a rotation of its column order, any order is valid
-  // -- and the overlap is served by the L2.  Windows as wide as the matrix (random patterns): P covers it, plain column order.
-  int64_t P = INT64_MAX;
-  {
-    std::vector<int64_t> widths;
-    for (int64_t r = 0; r < H.nrows;) {
-      const int64_t r1 = group_end(r);
-      int64_t cmin = INT64_MAX, cmax = -1;
-      for (int64_t k = H.rowptr[r]; k < H.rowptr[r1]; ++k) {
-        cmin = std::min<int64_t>(cmin, H.colind[k]);
-        cmax = std::max<int64_t>(cmax, H.colind[k]);
-      }
-      if (cmax >= cmin) widths.push_back(cmax - cmin + 1);
-      r = r1;
-    }
-    if (!widths.empty()) {
-      std::nth_element(widths.begin(), widths.begin() + widths.size() / 2, widths.end());
-      const int64_t med = std::max<int64_t>(1, widths[widths.size() / 2]);
-      // the period: the WIDEST of the typical windows (those within 1.5 x the median), so that (col mod P) is one-to-one on
-      // every typical group's window -- a pure rotation of its column order.  (The median itself -- rounds 3 -- left half of the
-      // groups a little wider than the period: the first and last few columns of such a window share phases and their
-      // entries INTERLEAVE in the sorted order, which cuts the contiguous per-group runs the shared-value layout of A'
-      // builds on into slivers.)
-      P = med;
-      for (const int64_t w : widths)
-        if (w <= med + med / 2) P = std::max(P, w);
-    }
-    if (const char* ev = std::getenv("FPSQ_RGCS_PHASE"))  // 0: plain column order (A/B)
-      if (std::atoi(ev) == 0) P = INT64_MAX;
-  }
-  int64_t r = 0;
-  while (r < H.nrows) {
-    const int64_t r1 = group_end(r);
-    const int R = (int)(r1 - r);
-    const int e0 = H.rowptr[r], e1 = H.rowptr[r1], cnt = e1 - e0;
-    int cmin = INT32_MAX, cmax = -1;
-    for (int k = e0; k < e1; ++k) {
-      cmin = std::min(cmin, H.colind[k]);
-      cmax = std::max(cmax, H.colind[k]);
-    }
-    if (cnt == 0) cmin = cmax = 0;
-    if ((int64_t)cmax - cmin >= (1ll << kRgcsColBits)) return 0;  // not representable: keep CSR-stream
-    lrow.resize(cnt);
-    for (int rr = 0; rr < R; ++rr)
-      for (int k = H.rowptr[r + rr]; k < H.rowptr[r + rr + 1]; ++k) lrow[k - e0] = rr;
-    ord.resize(cnt);
-    for (int k = 0; k < cnt; ++k) ord[k] = k;
-    // (a group much wider than the typical window would interleave several column ranges in one tile: plain order for it)
-    const int64_t Pg = (int64_t)cmax - cmin + 1 > P + P / 2 ? INT64_MAX : P;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
-      const int64_t ca = H.colind[e0 + a], cb = H.colind[e0 + b];
-      const int64_t pa = ca % Pg, pb = cb % Pg;
-      return pa != pb ? pa < pb : ca < cb;
-    });
-    const int ntile = (cnt + kRgcsTile - 1) / kRgcsTile;
-    const int32_t tp_start = (int32_t)tptr.size();
-    for (int t = 0; t < ntile; ++t) {
-      const int a = t * kRgcsTile, b = std::min(cnt, a + kRgcsTile);
-      cntr.assign(R + 1, 0);
-      for (int k = a; k < b; ++k) cntr[lrow[ord[k]] + 1]++;
-      for (int rr = 0; rr < R; ++rr) cntr[rr + 1] += cntr[rr];
-      for (int rr = 0; rr <= R; ++rr) tptr.push_back((uint16_t)cntr[rr]);
-      nxt.assign(cntr.begin(), cntr.end() - 1);
-      for (int k = a; k < b; ++k) {
-        const int src = ord[k];
-        const int slot = nxt[lrow[src]]++;
-        pidx[e0 + k] = ((uint32_t)slot << kRgcsColBits) | (uint32_t)(H.colind[e0 + src] - cmin);
-        vperm[e0 + k] = e0 + src;
-      }
-    }
-    if (col_range) col_range->push_back(make_int2(cmin, cmax));
-    RgcsGroup gd{};
-    gd.r0 = (int32_t)r;
-    gd.R = R;
-    gd.e0 = e0;
-    gd.e1 = e1;
-    gd.cmin = cmin;
-    gd.tp = tp_start;
-    groups.push_back(gd);
-    if (ntile == 0)
-      for (int rr = 0; rr <= R; ++rr) tptr.push_back(0);
-    r = r1;
-  }
-  tptr.push_back(0);
-  tptr.push_back(0);  // the kernel reads two uint16 at once
-  // Padded layout (k_spmv_rgcs<.., PAD>): group g at [g * budget, ...), zero entries up to the end of its last tile.
-  bool padded = (int64_t)groups.size() * budget < (int64_t)INT32_MAX;
-  for (const RgcsGroup& gd : groups) padded = padded && gd.e1 - gd.e0 <= budget;
-  int64_t nstore = nnz;
-  if (padded) {
-    nstore = (int64_t)groups.size() * budget;
-    std::vector<uint32_t> pp((size_t)nstore, 0u);
-    std::vector<int32_t> vp((size_t)nstore, -1);
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-      RgcsGroup& gd = groups[gi];
-      const int cnt = gd.e1 - gd.e0;
-      const size_t dst = gi * (size_t)budget;
-      for (int k = 0; k < cnt; ++k) {
-        pp[dst + k] = pidx[gd.e0 + k];
-        vp[dst + k] = vperm[gd.e0 + k];
-      }
-      const int full = (cnt + kRgcsTile - 1) / kRgcsTile * kRgcsTile;
-      for (int k = cnt; k < full; ++k) pp[dst + k] = (uint32_t)(k % kRgcsTile) << kRgcsColBits;  // unused slot, value 0
-    }
-    pidx.swap(pp);
-    vperm.swap(vp);
-  }
+  if (!L.ok) return 0;
   uint32_t* dp;
   RgcsGroup* dg;
   uint16_t* d5;
-  if (int rc = dalloc(h, &dp, (size_t)nstore + 1)) return rc;
-  if (int rc = dalloc(h, &D.vals, (size_t)nstore + 1)) return rc;
-  if (int rc = dalloc(h, &D.vperm, (size_t)nstore)) return rc;
-  if (int rc = dalloc(h, &dg, groups.size())) return rc;
-  if (int rc = dalloc(h, &d5, tptr.size() + 2)) return rc;
-  HIPCHK(h, hipMemcpy(dp, pidx.data(), (size_t)nstore * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemset(dp + nstore, 0, 4));
-  HIPCHK(h, hipMemset(D.vals, 0, ((size_t)nstore + 1) * 8));
-  HIPCHK(h, hipMemcpy(D.vperm, vperm.data(), (size_t)nstore * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(dg, groups.data(), groups.size() * sizeof(RgcsGroup), hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(d5, tptr.data(), tptr.size() * 2, hipMemcpyHostToDevice));
-  if (csr_pos && padded) {  // where every CSR slot of A sits in the (padded) row-group array: pad_blocks builds A' on it
-    csr_pos->assign((size_t)nnz, -1);
-    for (int64_t p = 0; p < nstore; ++p)
-      if (vperm[p] >= 0) (*csr_pos)[vperm[p]] = (int32_t)p;
-  }
-  D.view = RgcsView{dp, D.vals, dg, d5, (int32_t)groups.size(), (int32_t)H.nrows, padded ? budget : 0};
-  D.nstore = nstore;
-  D.nnz = nnz;
+  if (int rc = dalloc(h, &dp, (size_t)L.nstore + 1)) return rc;
+  if (int rc = dalloc(h, &D.vals, (size_t)L.nstore + 1)) return rc;
+  if (int rc = dalloc(h, &D.vperm, (size_t)L.nstore)) return rc;
+  if (int rc = dalloc(h, &dg, L.groups.size())) return rc;
+  if (int rc = dalloc(h, &d5, L.tptr.size() + 2)) return rc;
+  if (int rc = upload(h, dp, L.pidx)) return rc;
+  HIPCHK(h, hipMemset(dp + L.nstore, 0, 4));
+  HIPCHK(h, hipMemset(D.vals, 0, ((size_t)L.nstore + 1) * 8));
+  if (int rc = upload(h, D.vperm, L.vperm)) return rc;
+  if (int rc = upload(h, dg, L.groups)) return rc;
+  if (int rc = upload(h, d5, L.tptr)) return rc;
+  D.view = RgcsView{dp, D.vals, dg, d5, (int32_t)L.groups.size(), (int32_t)H.nrows, L.padded ? L.budget : 0};
+  D.nstore = L.nstore;
+  D.nnz = (int64_t)H.colind.size();
   D.ok = true;
   return 0;
 }
@@ -1528,29 +1142,23 @@ int alloc_workspaces(fpsq_handle h) {
 
 // One launch per joint iteration (k_iter_fused) -- what it needs beyond the two products' layouts: every A' block boundary on a
 // 128-byte line of the long pair, the main layouts of both products (column-sorted padded blocks, padded row groups), 32-bit
-// byte offsets into the long pair, and per row group the range of A' blocks that own the lines it gathers from.
-int setup_fused_iteration(fpsq_handle h, const HostCsr& HT, const std::vector<int2>& col_range) {
+// byte offsets into the long pair, and per row group the range of A' blocks that own the lines it gathers from (fused_dep).
+// rb: the row blocks of A'.
+int setup_fused_iteration(fpsq_handle h, const std::vector<int32_t>& rb, const std::vector<Range2>& col_range) {
   h->fuse_ok = false;
   if (!h->fuse_iter || !h->fuse_hw_ok || !h->RA.ok || h->RA.view.stride == 0 || !h->AT.padded || !(h->AT.sorted || h->AT.col16) || h->AT.nblk < 1)
     return 0;
   if ((int64_t)h->n * 16 >= (int64_t)INT32_MAX || (int64_t)h->m * 16 >= (int64_t)INT32_MAX) return 0;
   if ((int)col_range.size() != h->RA.view.ng) return 0;
-  const std::vector<int32_t> rb = make_rowblocks(HT.rowptr, HT.nrows, h->AT.row_align);
   if ((int)rb.size() - 1 != h->AT.nblk || !rowblocks_aligned(rb, 8)) return 0;
-  std::vector<int2> dep(col_range.size());
-  for (size_t g = 0; g < col_range.size(); ++g) {
-    const int64_t lo = col_range[g].x & ~7, hi = std::min<int64_t>((int64_t)col_range[g].y | 7, h->n - 1);
-    const int b0 = (int)(std::upper_bound(rb.begin(), rb.end(), (int32_t)lo) - rb.begin()) - 1;
-    const int b1 = (int)(std::upper_bound(rb.begin(), rb.end(), (int32_t)hi) - rb.begin()) - 1;
-    dep[g] = make_int2(std::max(b0, 0), std::min(std::max(b1, 0), h->AT.nblk - 1));
-  }
+  const std::vector<Range2> dep = fused_dep(rb, col_range, h->n);
   if (h->fuse_iter == 1) {
     // Where it pays (measured): a grid of several resident sets -- the row groups then enter as the last A'
     // blocks drain and find most of what they wait for done -- whose row groups depend on a small part of the A' blocks.
     // A grid that is resident at once gains nothing from sharing a launch and pays for the flags (cfg2, random columns: every
     // group waits for every block; 2500 -> 2230 evals/s).
     double width = 0.0;
-    for (const int2& d : dep) width += d.y - d.x + 1;
+    for (const Range2& d : dep) width += d.y - d.x + 1;
     width /= (double)std::max<size_t>(dep.size(), 1);
     // (the size threshold: profiles/r04_fused_sizes.txt -- headline generator, one launch against two: -3.2 % at 1225 blocks,
     // -2.4 % at 1617, +2.3 % at 1764, +7.7 % at 1862, +8.4 % at 1960, +7.3 % at 2450, +2.5 to +4 % at 4900, -0.5 % at 9800)
@@ -1570,20 +1178,11 @@ int setup_fused_iteration(fpsq_handle h, const HostCsr& HT, const std::vector<in
   h->fz_colrange = col_range;
   h->fuse_ok = true;
   // ---- several iterations per launch (fpsq_multi.hip.h): per A' block the row groups whose rows of the short pair it gathers
-  // (the mirror image of `dep`; a cover by ONE range -- waiting for more is safe; a block nobody gathers from -- empty columns --
-  // waits for every group: its own previous incarnation is then complete too), second copies of the flags and tagged words,
-  // records, the second long pair
+  // (fused_bdep), second copies of the flags and tagged words, records, the second long pair
   h->multi_ok = false;
   if (h->multi_max > 1) {
     const int ng = h->RA.view.ng, nb = h->AT.nblk;
-    std::vector<int2> bdep((size_t)nb, make_int2(INT32_MAX, -1));
-    for (int g = 0; g < ng; ++g)
-      for (int L = dep[g].x; L <= dep[g].y; ++L) {
-        bdep[L].x = std::min(bdep[L].x, g);
-        bdep[L].y = std::max(bdep[L].y, g);
-      }
-    for (int L = 0; L < nb; ++L)
-      if (bdep[L].y < bdep[L].x) bdep[L] = make_int2(0, ng - 1);
+    const std::vector<Range2> bdep = fused_bdep(dep, nb);
     dfree(h, &h->mz_bdep);
     dfree(h, &h->mz_flag2);
     dfree(h, &h->mz_ptag2);
@@ -1622,44 +1221,57 @@ int setup_fused_iteration(fpsq_handle h, const HostCsr& HT, const std::vector<in
 
 // The one-launch iteration of a halo-sharded handle (fpsq_comm_set_halo, or a new structure on such a handle): which A' blocks
 // deposit the raw sums of the two overlap regions, and which row groups gather from a region (they wait for the finish
-// workgroups).  Needs the regions on 128-byte lines of the long pair (8 rows): distributed.halo_plan rounds its windows so.
+// workgroups) -- fused_halo_dep.  Needs the regions on 128-byte lines of the long pair (8 rows): distributed.halo_plan rounds
+// its windows so.
 int setup_fused_halo(fpsq_handle h) {
   h->fuse_halo_ok = false;
   if (!h->fuse_ok || !h->halo || h->ovl + h->ovr == 0) return 0;
   if (h->ovl % 8 != 0 || (h->n - h->ovr) % 8 != 0 || h->halo_gf > kEwBlocksMax) return 0;
-  const std::vector<int32_t>& rb = h->fz_rb;
-  auto block_of = [&](int64_t row) { return (int)(std::upper_bound(rb.begin(), rb.end(), (int32_t)row) - rb.begin()) - 1; };
-  h->fz_depL = h->ovl > 0 ? make_int2(0, std::max(block_of(h->ovl - 1), 0)) : make_int2(1, 0);
-  h->fz_depR = h->ovr > 0 ? make_int2(std::max(block_of(h->n - h->ovr), 0), h->AT.nblk - 1) : make_int2(1, 0);
-  std::vector<int2> dep2(h->fz_colrange.size());
-  for (size_t g = 0; g < dep2.size(); ++g) {
-    const int64_t lo = h->fz_colrange[g].x & ~7, hi = std::min<int64_t>((int64_t)h->fz_colrange[g].y | 7, h->n - 1);
-    const bool touches = lo < h->ovl || hi >= h->n - h->ovr;
-    dep2[g] = touches ? make_int2(h->AT.nblk, h->AT.nblk + h->halo_gf - 1) : make_int2(1, 0);
-  }
+  const HaloDep hd = fused_halo_dep(h->fz_rb, h->fz_colrange, h->n, h->ovl, h->ovr, h->halo_gf);
+  h->fz_depL = make_int2(hd.depL.x, hd.depL.y);
+  h->fz_depR = make_int2(hd.depR.x, hd.depR.y);
   dfree(h, &h->fz_dep2);
-  if (int rc = dalloc(h, &h->fz_dep2, dep2.size())) return rc;
-  HIPCHK(h, hipMemcpy(h->fz_dep2, dep2.data(), dep2.size() * sizeof(int2), hipMemcpyHostToDevice));
+  if (int rc = dalloc(h, &h->fz_dep2, hd.dep2.size())) return rc;
+  HIPCHK(h, hipMemcpy(h->fz_dep2, hd.dep2.data(), hd.dep2.size() * sizeof(int2), hipMemcpyHostToDevice));
   h->fuse_halo_ok = true;
   return 0;
 }
 
-// after the structure (host CSR of A) is known: transposed copy, uploads, workspaces
+// after the structure (host CSR of A) is known: transposed copy, the layouts (built on the host from the switches read here,
+// then uploaded), workspaces
 int finish_structure(fpsq_handle h, const HostCsr& HA) {
   HostCsr HT;
   std::vector<int32_t> perm;
   transpose_structure(HA, HT, perm);
-  if (int rc = upload_csr(h, HA, h->A)) return rc;
+  const bool compact = h->opt.jac_format == 1;  // plain CSR with 32-bit columns: no compressed, padded or row-group layout
   h->AT.row_align = h->fuse_iter ? 8 : 1;  // (whether a sharded handle may use the launch is decided per run: KrylovRun::setup)
   if (const char* ev = std::getenv("FPSQ_AT_ROW_ALIGN")) h->AT.row_align = std::max(1, std::atoi(ev));  // (tests: the fused layout without the fused launch)
-  if (int rc = upload_csr(h, HT, h->AT)) return rc;
-  std::vector<int32_t> csr_pos;
-  std::vector<int2> col_range;
-  if (int rc = build_rgcs(h, HA, h->RA, &csr_pos, &col_range)) return rc;
-  const bool can_share = h->RA.ok && !csr_pos.empty() && !h->refresh_3pass;
-  if (int rc = pad_blocks(h, HT, perm, h->AT, can_share ? &csr_pos : nullptr, h->RA.nstore, h->RA.vals)) return rc;
-  if (int rc = dalloc(h, &h->permT, perm.size())) return rc;
-  if (!perm.empty()) HIPCHK(h, hipMemcpy(h->permT, perm.data(), perm.size() * 4, hipMemcpyHostToDevice));
+  if (int rc = upload_blocks(h, HA, build_blocks(HA, h->A.row_align, !compact), h->A)) return rc;
+  BlockLayout BT = build_blocks(HT, h->AT.row_align, !compact);  // (the row blocks of A': computed once, for all that follows)
+  if (int rc = upload_blocks(h, HT, BT, h->AT)) return rc;
+  // (once uploaded, the large host arrays nobody reads again go before the next builder allocates its own)
+  std::vector<uint16_t>().swap(BT.col16);
+  RgcsLayout LA;
+  if (!compact) {
+    hipDeviceProp_t prop;
+    int cus = 256;
+    if (hipGetDeviceProperties(&prop, h->opt.device) == hipSuccess && prop.multiProcessorCount > 0)
+      cus = prop.multiProcessorCount;
+    const char* tiles = std::getenv("FPSQ_RGCS_TILES");  // tuning override: tiles per group
+    const char* phase = std::getenv("FPSQ_RGCS_PHASE");  // 0: plain column order (A/B)
+    LA = build_rgcs(HA, cus, tiles ? std::max(1, std::atoi(tiles)) : 0, !(phase && std::atoi(phase) == 0));
+  }
+  if (int rc = upload_rgcs(h, HA, LA, h->RA)) return rc;
+  std::vector<uint32_t>().swap(LA.pidx);
+  std::vector<int32_t>().swap(LA.vperm);
+  if (!compact) {
+    const bool can_share = h->RA.ok && !LA.csr_pos.empty() && !h->refresh_3pass;
+    const PaddedLayout PT = pad_blocks(HT, BT, perm, h->at_sorted, h->at_shared, can_share ? &LA.csr_pos : nullptr, h->RA.nstore);
+    if (PT.nown >= 0 && std::getenv("FPSQ_VERBOSE"))
+      std::fprintf(stderr, "fpsq: shared A' values: %d of %d blocks keep their own\n", PT.nown, BT.nblk());
+    if (int rc = upload_padded(h, PT, h->AT, h->RA.vals, h->RA.nstore)) return rc;
+  }
+  if (int rc = dalloc_upload(h, &h->permT, perm)) return rc;
   h->nnz = h->A.nnz;
   // COO input without duplicates: the value permutations of A' and of the row groups are composed with the COO -> CSR order
   // once, here, so that a refresh gathers straight from the caller's jac_coord! output (k_refresh) -- no CSR staging pass.
@@ -1673,7 +1285,7 @@ int finish_structure(fpsq_handle h, const HostCsr& HA) {
     h->perms_to_input = true;
   }
   if (int rc = alloc_workspaces(h)) return rc;
-  if (int rc = setup_fused_iteration(h, HT, col_range)) return rc;
+  if (int rc = setup_fused_iteration(h, BT.rb, LA.col_range)) return rc;
   if (int rc = setup_fused_halo(h)) return rc;  // (a halo-sharded handle given a new structure)
   HIPCHK(h, hipDeviceSynchronize());  // the set-up used null-stream copies/memsets; the solver stream is non-blocking
   h->have_structure = true;

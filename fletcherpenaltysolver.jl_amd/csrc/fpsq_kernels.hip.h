@@ -7,16 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace fpsq {
+#include "fpsq_layout.h"  // kBlock, kSpmvNnz, kMaxRowsPerBlk, kEwBlocksMax: the constants the host-built layouts share
 
-constexpr int kBlock = 256;        // threads per workgroup (4 waves)
-static_assert(kBlock == 256, "block_sum / block_sum_lanes and the tile-per-thread constants assume 4 waves");
-#ifndef FPSQ_SPMV_NNZ
-#define FPSQ_SPMV_NNZ 2048
-#endif
-constexpr int kSpmvNnz = FPSQ_SPMV_NNZ;  // nonzeros staged through LDS per workgroup
-constexpr int kMaxRowsPerBlk = 1024;
-constexpr int kEwBlocksMax = 1024; // grid cap for element-wise kernels (grid-stride beyond)
+namespace fpsq {
 
 // Per-recurrence control block read by the generic kernels; written only by that recurrence's scalar kernels.
 struct LaneCtl {

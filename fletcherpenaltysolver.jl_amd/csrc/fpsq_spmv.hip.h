@@ -4,6 +4,7 @@
 // because the riding steps need the recurrences of fpsq_krylov.hip.h.
 #pragma once
 #include "fpsq_krylov.hip.h"
+#include "fpsq_layout.h"
 
 namespace fpsq {
 
@@ -1031,30 +1032,9 @@ __global__ __launch_bounds__(kBlock) void k_spmv_atl(CsrView A, const double* __
 // with its group-relative column in one 32-bit word (12 B/nnz like CSR), its slot in the tile's ROW-major order:
 // products are scattered to LDS by slot and every row's segment is reduced exactly as in the CSR-stream kernel;
 // the per-row sums accumulate in registers across the tiles of the group.  Deterministic, no atomics.
-#ifndef FPSQ_RGCS_TILE
-#define FPSQ_RGCS_TILE 2048
-#endif
-#ifndef FPSQ_RGCS_GROUP_NNZ
-#define FPSQ_RGCS_GROUP_NNZ 12800
-#endif
-#ifndef FPSQ_RGCS_MAX_ROWS
-#define FPSQ_RGCS_MAX_ROWS 128
-#endif
-constexpr int kRgcsTile = FPSQ_RGCS_TILE;
-constexpr int kRgcsColBits = 21;     // group-relative column < 2^21, slot < 2^11
-constexpr int kRgcsGroupNnz = FPSQ_RGCS_GROUP_NNZ;
-constexpr int kRgcsMaxRows = FPSQ_RGCS_MAX_ROWS;
+// (kRgcsTile, kRgcsColBits, kRgcsGroupNnz, kRgcsMaxRows and RgcsGroup: fpsq_layout.h, shared with the host-side builder)
 // row passes of the segment reduction: G lanes per row with G * R <= kBlock, so rows <= kBlock need a single pass
 constexpr int kRgcsMaxPass = (kRgcsMaxRows + kBlock - 1) / kBlock;
-static_assert(kRgcsTile <= 2048 && kRgcsTile % kBlock == 0, "slot field is 11 bits");
-
-struct RgcsGroup {        // 32 bytes, fetched with two independent 16-byte loads at the head of the workgroup
-  int32_t r0, R;          // first row, #rows
-  int32_t e0, e1;         // entry range
-  int32_t cmin;           // smallest column of the group
-  int32_t tp;             // offset into tptr
-  int32_t pad[2];
-};
 
 struct RgcsView {
   const uint32_t* pidx;   // (slot << kRgcsColBits) | (col - cmin)
