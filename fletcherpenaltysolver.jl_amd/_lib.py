@@ -138,6 +138,7 @@ SYMBOLS = [
     ("fpsq_band_set_input_stream", C.c_int, [_VP, _I32, _VP]),
     ("fpsq_band_solve_two_least_squares_block", C.c_int, [_VP, _I32, _DP, _DP, _DP, _DP, _DP, _DP]),
     ("fpsq_band_qp_hprod_block", C.c_int, [_VP, _VP, _I32, _DP, _D, _D, _D, _I32, _DP]),
+    ("fpsq_band_qp_objgrad_block", C.c_int, [_VP, _VP, _I32, _DP, _DP, _DP, _D, _D, _D, _DP, _DP, _DP, _DP, _DP]),
     ("fpsq_get_info", C.c_int, [_VP, C.POINTER(Info)]),
     ("fpsq_set_profiling", C.c_int, [_VP, _I32]),
     ("fpsq_debug_expect_iterations", C.c_int, [_VP, _I64]),

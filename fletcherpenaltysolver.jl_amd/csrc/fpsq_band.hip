@@ -30,9 +30,14 @@ struct fpsq_band_s : DirectCore {
   hipEvent_t evA = nullptr, evB = nullptr;
   double* csr_in = nullptr;  // fpsq_band_create_coo: the CSR slots the sorted COO entries are summed into
   // block entries (fpsq_band_*_block), allocated when first needed: the interleaved tile A multiplies [n][16], A v [mpad][8],
-  // Ptv [n][8] (sparse Q only), and the staging of host-resident blocks (rhs1 / V, rhs2, p1 / HV, p2: 8 n; q1, q2: 8 m)
+  // Ptv [n][8] (sparse Q only), and the staging of host-resident blocks (rhs1 / V / X, rhs2 / D, p1 / HV / GX, p2 / GS: 8 n;
+  // q1 / YS, q2 / Bv: 8 m; XK: 8 n)
   double *blk_xg = nullptr, *blk_keep = nullptr, *blk_tv = nullptr;
-  double* blk_stage[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double* blk_stage[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // fpsq_band_qp_objgrad_block, allocated by its first call: the per-column partial sums of the three product kernels
+  // ([kBqMaxGrid][8], [kBqMaxGrid][8][2] twice), the scalars of a tile ([8][5]) and their pinned host side, one slot per tile
+  double *og_partF = nullptr, *og_partP = nullptr, *og_partE = nullptr, *og_scal = nullptr, *og_scal_host = nullptr;
+  int og_tiles = 0;  // slots of og_scal_host
   bool have_vals = false;    // a factorisation has put the Jacobian's values into vals / t_vals (fpsq_band_jac_mul, fpsq_band_qp_*)
   // bordered band (fpsq_band_create_bordered; kernels and algebra: fpsq_band.hip.h "bordered band"): the last `border` stored
   // rows are eliminated after the band of the first mb = m - border rows; nb, band_w, Mb and the sweeps describe that band
@@ -660,6 +665,7 @@ int fpsq_band_destroy(fpsq_band b) {
   if (b->evB) hipEventDestroy(b->evB);
   if (b->evS0) hipEventDestroy(b->evS0);
   if (b->evS1) hipEventDestroy(b->evS1);
+  if (b->og_scal_host) hipHostFree(b->og_scal_host);
   if (b->stream2) {
     hipStreamSynchronize(b->stream2);
     hipStreamDestroy(b->stream2);
@@ -1215,12 +1221,34 @@ int blk_setup(fpsq_band b, bool keep, bool tv) {
   return FPSQ_OK;
 }
 
-// A xg into the sweeps' layout, then the two sweeps: the tile's solutions end up in b->r16
+// the two sweeps on the tile's right-hand sides in b->r16, the border correction included: the solutions end up in b->r16
+void blk_sweeps(fpsq_band b) {
+  chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
+  if (b->border) border_correct<kBlkCols>(b, b->r16);
+}
+
+// A xg into the sweeps' layout, then the two sweeps
 void blk_solve_tile(fpsq_band b, int lgA, double* keep) {
   WITH_LANE_GROUP(lgA, hipLaunchKernelGGL(k_bqb_prologue<LG>, dim3(bq_grid(b->mpad, lgA)), dim3(256), 0, b->stream, b->rowptr,
                                           b->colind, b->vals, b->blk_xg, b->r16, keep, (int)b->m, (int)b->mpad))
-  chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
-  if (b->border) border_correct<kBlkCols>(b, b->r16);
+  blk_sweeps(b);
+}
+
+// the buffers of fpsq_band_qp_objgrad_block besides blk_setup's: the partial sums, the scalars of `tiles` tiles
+int og_setup(fpsq_band b, int tiles) {
+  if (!b->og_scal) {
+    if (dalloc(b, &b->og_partF, (size_t)kBqMaxGrid * kBlkVec) || dalloc(b, &b->og_partP, (size_t)kBqMaxGrid * kBlkCols) ||
+        dalloc(b, &b->og_partE, (size_t)kBqMaxGrid * kBlkCols) || dalloc(b, &b->og_scal, (size_t)kBlkVec * 5))
+      return FPSQ_ERR_HIP;
+  }
+  if (tiles > b->og_tiles) {
+    if (b->og_scal_host) hipHostFree(b->og_scal_host);
+    b->og_scal_host = nullptr;
+    b->og_tiles = 0;
+    CHK(b, hipHostMalloc((void**)&b->og_scal_host, (size_t)tiles * kBlkVec * 5 * 8, hipHostMallocDefault));
+    b->og_tiles = tiles;
+  }
+  return FPSQ_OK;
 }
 }  // namespace
 
@@ -1308,5 +1336,81 @@ int fpsq_band_qp_hprod_block(fpsq_band b, fpsq_band_qp qp, int32_t k, const doub
     if (int rc = stage_back(b, ah, v0, kt)) return rc;
   }
   return eval_end(b, 0, &b->info.last_solve_ms, kBlkExpired);
+}
+
+int fpsq_band_qp_objgrad_block(fpsq_band b, fpsq_band_qp qp, int32_t k, const double* X, const double* D, const double* Bv,
+                               double sigma, double rho, double eta, const double* XK, double* fx, double* GX, double* YS,
+                               double* GS) {
+  if (!b) return FPSQ_ERR_ARG;
+  if (!qp || qp->b != b || k < 1 || !X || !fx) {
+    b->err = "band_qp_objgrad_block: a model of this handle, k >= 1, X and fx are required";
+    return FPSQ_ERR_ARG;
+  }
+  const size_t n = (size_t)b->n, m = (size_t)b->m;
+  {
+    struct Range { const char* name; const double* p; size_t len; };
+    const Range in[4] = {{"X", X, n}, {"D", D, n}, {"Bv", Bv, m}, {"XK", XK, n}};
+    const Range out[3] = {{"GX", GX, n}, {"YS", YS, m}, {"GS", GS, n}};
+    auto overlap = [&](const Range& u, const Range& w) {
+      if (!u.p || !w.p) return false;
+      const uintptr_t lo = (uintptr_t)u.p, ho = (uintptr_t)w.p;
+      return lo < ho + (uintptr_t)k * w.len * 8 && ho < lo + (uintptr_t)k * u.len * 8;
+    };
+    for (int o = 0; o < 3; ++o) {
+      for (int i = 0; i < 4 + o; ++i) {
+        const Range& w = i < 4 ? in[i] : out[i - 4];
+        if (overlap(out[o], w)) {
+          b->err = std::string("band_qp_objgrad_block: ") + out[o].name + " and " + w.name + " overlap";
+          return FPSQ_ERR_ARG;
+        }
+      }
+    }
+  }
+  if (int rc = eval_begin(b)) return rc;
+  if (int rc = blk_setup(b, true, qp->sparse_q)) return rc;
+  const int tiles = (k + kBlkVec - 1) / kBlkVec;
+  if (int rc = og_setup(b, tiles)) return rc;
+  rho = rho > 0.0 ? rho : 0.0;  // (the reference adds these terms only when the parameter is positive)
+  eta = eta > 0.0 ? eta : 0.0;
+  StagedArg ax, ad, ab, axk, ogx, ogs, oys;
+  if (blk_arg(b, X, n, 0, &ax) || blk_arg(b, D, n, 1, &ad) || blk_arg(b, GX, n, 2, &ogx) || blk_arg(b, GS, n, 3, &ogs) ||
+      blk_arg(b, YS, m, 4, &oys) || blk_arg(b, Bv, m, 5, &ab) || blk_arg(b, eta > 0.0 ? XK : nullptr, n, 6, &axk))
+    return FPSQ_ERR_HIP;
+  hipStream_t s = b->stream;
+  const double* partF = qp->sparse_q ? b->og_partF : nullptr;
+  for (int v0 = 0, t = 0; v0 < k; v0 += kBlkVec, ++t) {
+    const int kt = std::min<int>(kBlkVec, k - v0);
+    for (const StagedArg* a : {&ax, &ad, &ab, &axk})
+      if (int rc = stage_in(b, *a, v0, kt)) return rc;
+    const double *dx = ax.tile(v0), *dd = ad.tile(v0), *db = ab.tile(v0), *dxk = axk.tile(v0);
+    double *dgx = ogx.tile(v0), *dgs = ogs.tile(v0), *dys = oys.tile(v0);
+    if (qp->sparse_q) {
+      WITH_LANE_GROUP(qp->lgR, hipLaunchKernelGGL(k_bqb_og_pack_sq<LG>, dim3(qp->gridR), dim3(256), 0, s, qp->r_rowptr,
+                                                  qp->r_colind, qp->r_vals, dx, dd, qp->d, qp->q, b->blk_xg, b->og_partF, (int)n,
+                                                  kt))
+    } else {
+      hipLaunchKernelGGL(k_bqb_og_pack, grid256(n), dim3(256), 0, s, dx, dd, qp->d, qp->q, b->blk_xg, (int)n, kt);
+    }
+    WITH_LANE_GROUP(qp->lgA, WITH_BOOL(!qp->sparse_q, FD, hipLaunchKernelGGL(
+        (k_bqb_og_prologue<LG, FD>), dim3(qp->gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, b->blk_xg, dx, dd, qp->d,
+        qp->q, db, qp->bp, b->row_perm(), b->r16, b->blk_keep, b->og_partP, (int)m, (int)b->mpad, (int)n, kt)))
+    blk_sweeps(b);
+    WITH_LANE_GROUP(qp->lgT, WITH_BOOL(qp->sparse_q, SQ, hipLaunchKernelGGL(
+        (k_bqb_og_epilogue<LG, SQ>), dim3(qp->gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, b->r16, b->blk_keep,
+        b->row_perm(), qp->q, b->blk_xg, dxk, sigma, rho, eta, dgx, dgs, dys, b->blk_tv, b->og_partE, (int)n, (int)m, kt)))
+    if (qp->sparse_q && dgx) {  // GX -= R p2: the rows of tv are complete only now
+      WITH_LANE_GROUP(qp->lgR, hipLaunchKernelGGL(k_bqb_rsub<LG>, dim3(qp->gridR), dim3(256), 0, s, qp->r_rowptr, qp->r_colind,
+                                                  qp->r_vals, b->blk_tv, dgx, (int)n, kt))
+    }
+    hipLaunchKernelGGL(k_bqb_phi, dim3(1), dim3(256), 0, s, partF, qp->gridR, b->og_partP, qp->gridP, b->og_partE, qp->gridE, rho,
+                       eta, b->og_scal);
+    CHK(b, hipMemcpyAsync(b->og_scal_host + (size_t)t * kBlkVec * 5, b->og_scal, (size_t)kBlkVec * 5 * 8, hipMemcpyDeviceToHost,
+                          s));
+    for (const StagedArg* o : {&ogx, &ogs, &oys})
+      if (int rc = stage_back(b, *o, v0, kt)) return rc;
+  }
+  if (int rc = eval_end(b, 0, &b->info.last_solve_ms, kBlkExpired)) return rc;
+  for (int j = 0; j < k; ++j) fx[j] = b->og_scal_host[(size_t)j * 5];
+  return FPSQ_OK;
 }
 }  // extern "C"

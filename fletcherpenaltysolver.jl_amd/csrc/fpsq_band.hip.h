@@ -755,6 +755,305 @@ __global__ __launch_bounds__(256) void k_bqb_rsub(const int32_t* __restrict__ r_
   }
 }
 
+// ---- objgrad form of the block kernels (fpsq_band_qp_objgrad_block): vector v of a tile is the evaluation at X[v] on the
+// model with its linear term replaced by D[v] (null: the model's d) and its right-hand side by Bv[v] (null: the model's b).
+// The tile is interleaved as above: xg[j][2 v], [2 v + 1] = {g, x}, r[p][2 v], [2 v + 1] = {A g, -c}, keep[p][v] = c,
+// tv[j][v] = p2.  The scalars of a column are summed like those of the single evaluation, per column: lanes by xor shuffles,
+// waves in index order (bq_block_sum), the workgroups' partials part[blk][column] in index order by k_bqb_phi.  Columns
+// kt <= v < kBlkVec are zero everywhere and their partials are zero.
+
+// xg[j] = {q[j] X[v][j] + d_v[j], X[v][j]}_v
+__global__ __launch_bounds__(256) void k_bqb_og_pack(const double* __restrict__ X, const double* __restrict__ D,
+                                                     const double* __restrict__ d, const double* __restrict__ q,
+                                                     double* __restrict__ xg, int n, int kt) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const double qv = q[j], dm = d[j];
+#pragma unroll
+  for (int v = 0; v < kBlkVec; ++v) {
+    f64x2 o = {0.0, 0.0};
+    if (v < kt) {
+      const double x = X[(size_t)v * n + j];
+      const double dv = D ? D[(size_t)v * n + j] : dm;
+      o = f64x2{qv * x + dv, x};
+    }
+    *reinterpret_cast<f64x2*>(xg + (size_t)j * kBlkCols + 2 * v) = o;
+  }
+}
+
+// The same pair for Q = diag(q) + R, a lane group per row of R: xg[j] = {q[j] X[v][j] + d_v[j] + (R X[v])_j, X[v][j]}_v, and
+// part[blk][v] = this workgroup's slice of f_v = sum_j X[v][j] (1/2 (Q X[v])_j + d_v[j])
+template <int LG>
+__global__ __launch_bounds__(256) void k_bqb_og_pack_sq(const int32_t* __restrict__ r_rowptr,
+                                                        const int32_t* __restrict__ r_colind,
+                                                        const double* __restrict__ r_vals, const double* __restrict__ X,
+                                                        const double* __restrict__ D, const double* __restrict__ d,
+                                                        const double* __restrict__ q, double* __restrict__ xg,
+                                                        double* __restrict__ part, int n, int kt) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[4 * kBlkVec];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[kBlkVec];
+#pragma unroll
+  for (int v = 0; v < kBlkVec; ++v) red[v] = 0.0;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s[kBlkVec];
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) s[v] = 0.0;
+    if (j < n) {
+      const int e = r_rowptr[j + 1];
+      for (int k = r_rowptr[j] + l; k < e; k += LG) {
+        const double a = r_vals[k];
+        const int c = r_colind[k];
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v)
+          if (v < kt) s[v] += a * X[(size_t)v * n + c];
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s[v] += __shfl_xor(s[v], o);
+    if (l == 0 && j < n) {
+      const double qv = q[j], dm = d[j];
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        f64x2 o = {0.0, 0.0};
+        if (v < kt) {
+          const double x = X[(size_t)v * n + j];
+          const double dv = D ? D[(size_t)v * n + j] : dm;
+          o = f64x2{qv * x + dv + s[v], x};
+          red[v] += x * (0.5 * (qv * x + s[v]) + dv);
+        }
+        *reinterpret_cast<f64x2*>(xg + (size_t)j * kBlkCols + 2 * v) = o;
+      }
+    }
+  }
+  bq_block_sum(red, sh);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) part[(size_t)blockIdx.x * kBlkVec + v] = red[v];
+  }
+}
+
+// One pass over the stored CSR of A for the 16 columns of a tile: with c_v[p] = (A X[v])_p - b_v[p], r[p] = {(A g_v)_p,
+// -c_v[p]}_v where the sweeps read it and keep[p][v] = c_v[p], all zero on the padding rows.  The model's b (bp) is in the
+// stored row order; a caller's Bv is in the caller's and is gathered through rperm (stored row -> the caller's, null =
+// identity).  part[blk][v] = {this workgroup's slice of f_v = X[v].(1/2 q X[v] + d_v) (FD: Q = diag(q); else 0: the pack
+// kernel has it), of c_v.c_v}.
+template <int LG, bool FD>
+__global__ __launch_bounds__(256) void k_bqb_og_prologue(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                         const double* __restrict__ vals, const double* __restrict__ xg,
+                                                         const double* __restrict__ X, const double* __restrict__ D,
+                                                         const double* __restrict__ d, const double* __restrict__ q,
+                                                         const double* __restrict__ Bv, const double* __restrict__ bp,
+                                                         const int32_t* __restrict__ rperm, double* __restrict__ r,
+                                                         double* __restrict__ keep, double* __restrict__ part, int m, int mpad,
+                                                         int n, int kt) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[4 * kBlkCols];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[kBlkCols];  // [2 v] = f_v, [2 v + 1] = c_v.c_v
+#pragma unroll
+  for (int c = 0; c < kBlkCols; ++c) red[c] = 0.0;
+  const int ntiles = (mpad + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int p = tile * RPB + g;
+    double acc[kBlkCols];
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c) acc[c] = 0.0;
+    if (p < m) {
+      const int e = rowptr[p + 1];
+      for (int k = rowptr[p] + l; k < e; k += LG) {
+        const double a = vals[k];
+        const f64x2* t = reinterpret_cast<const f64x2*>(xg + (size_t)colind[k] * kBlkCols);
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v) {
+          const f64x2 u = t[v];
+          acc[2 * v] += a * u.x;
+          acc[2 * v + 1] += a * u.y;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) acc[c] += __shfl_xor(acc[c], o);
+    if (l == 0 && p < mpad) {
+      const bool row = p < m;
+      const size_t src = row && Bv ? (size_t)(rperm ? rperm[p] : p) : 0;
+      const double bm = row && !Bv ? bp[p] : 0.0;
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        double a0 = 0.0, r1 = 0.0, cv = 0.0;
+        if (row && v < kt) {
+          a0 = acc[2 * v];
+          cv = acc[2 * v + 1] - (Bv ? Bv[(size_t)v * m + src] : bm);
+          r1 = -cv;
+          red[2 * v + 1] += cv * cv;
+        }
+        *reinterpret_cast<f64x2*>(r + (size_t)p * kBlkCols + 2 * v) = f64x2{a0, r1};
+        keep[(size_t)p * kBlkVec + v] = cv;
+      }
+    }
+  }
+  if (FD) {
+    const int64_t chunk = ((int64_t)n + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
+      const double qv = q[j], dm = d[j];
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        if (v < kt) {
+          const double x = X[(size_t)v * n + j];
+          const double dv = D ? D[(size_t)v * n + j] : dm;
+          red[2 * v] += x * (0.5 * qv * x + dv);
+        }
+      }
+    }
+  }
+  bq_block_sum(red, sh);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c) part[(size_t)blockIdx.x * kBlkCols + c] = red[c];
+  }
+}
+
+// One pass over the CSR of A' for a tile with the objgrad row epilogue of bq_epilogue_rows per column.  Row j, vector v, with
+// {g, x} from xg, s1 = (A'q1)_j, s2 = (A'q2)_j (y[p] = {q1, q2}_v: the sweeps' solution in the stored order), s3 = (A'c_v)_j:
+//   GS[v][j] = gs = g - s1 - sigma s2, p2 = -s2, GX[v][j] = gs + (sigma - q_j) p2 + rho s3 + eta (x - XK[v][j]);
+// SQ (Q = diag(q) + R) leaves tv[j][v] = p2 for k_bqb_rsub.  The workgroup also writes its slice of YS[v] = q1 + sigma q2 in
+// the caller's row order (rperm) and part[blk][v] = {its slice of c_v.ys_v, of |x - xk|^2 (0 unless eta > 0)}.
+// GX, GS, YS, XK may be null (XK: xk = 0).
+template <int LG, bool SQ>
+__global__ __launch_bounds__(256) void k_bqb_og_epilogue(const int32_t* __restrict__ t_rowptr,
+                                                         const int32_t* __restrict__ t_colind,
+                                                         const double* __restrict__ t_vals, const double* __restrict__ y,
+                                                         const double* __restrict__ keep, const int32_t* __restrict__ rperm,
+                                                         const double* __restrict__ q, const double* __restrict__ xg,
+                                                         const double* __restrict__ XK, double sigma, double rho, double eta,
+                                                         double* __restrict__ GX, double* __restrict__ GS,
+                                                         double* __restrict__ YS, double* __restrict__ tv,
+                                                         double* __restrict__ part, int n, int m, int kt) {
+  constexpr int RPB = 256 / LG;
+  __shared__ double sh[4 * kBlkCols];
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  double red[kBlkCols];  // [2 v] = c_v.ys_v, [2 v + 1] = |x - xk|^2
+#pragma unroll
+  for (int c = 0; c < kBlkCols; ++c) red[c] = 0.0;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s12[kBlkCols], s3[kBlkVec];
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c) s12[c] = 0.0;
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v) s3[v] = 0.0;
+    if (j < n) {
+      const int e = t_rowptr[j + 1];
+      for (int k = t_rowptr[j] + l; k < e; k += LG) {
+        const double a = t_vals[k];
+        const int p = t_colind[k];
+        const f64x2* t = reinterpret_cast<const f64x2*>(y + (size_t)p * kBlkCols);
+#pragma unroll
+        for (int v = 0; v < kBlkVec; ++v) {
+          const f64x2 u = t[v];
+          s12[2 * v] += a * u.x;
+          s12[2 * v + 1] += a * u.y;
+        }
+        const f64x2* kp = reinterpret_cast<const f64x2*>(keep + (size_t)p * kBlkVec);
+#pragma unroll
+        for (int v = 0; v < kBlkVec / 2; ++v) {
+          const f64x2 u = kp[v];
+          s3[2 * v] += a * u.x;
+          s3[2 * v + 1] += a * u.y;
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s12[c] += __shfl_xor(s12[c], o);
+#pragma unroll
+    for (int v = 0; v < kBlkVec; ++v)
+#pragma unroll
+      for (int o = LG / 2; o > 0; o >>= 1) s3[v] += __shfl_xor(s3[v], o);
+    if (l == 0 && j < n) {
+      const double qv = q[j];
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)j * kBlkCols + 2 * v);  // {g, x}
+        const double s1 = s12[2 * v], s2 = s12[2 * v + 1], p2 = -s2;
+        if (SQ) tv[(size_t)j * kBlkVec + v] = p2;
+        if (v < kt) {
+          const double gsv = t.x - s1 - sigma * s2;
+          const double dx = eta > 0.0 ? t.y - (XK ? XK[(size_t)v * n + j] : 0.0) : 0.0;
+          if (GS) GS[(size_t)v * n + j] = gsv;
+          if (GX) GX[(size_t)v * n + j] = gsv + (sigma - qv) * p2 + rho * s3[v] + eta * dx;
+          red[2 * v + 1] += dx * dx;
+        }
+      }
+    }
+  }
+  {
+    const int64_t chunk = ((int64_t)m + gridDim.x - 1) / gridDim.x;
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < m ? lo + chunk : m;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+      const size_t dst = (size_t)(rperm ? rperm[p] : p);
+#pragma unroll
+      for (int v = 0; v < kBlkVec; ++v) {
+        if (v < kt) {
+          const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * kBlkCols + 2 * v);
+          const double yv = t.x + sigma * t.y;
+          if (YS) YS[(size_t)v * m + dst] = yv;
+          red[2 * v] += keep[(size_t)p * kBlkVec + v] * yv;
+        }
+      }
+    }
+  }
+  bq_block_sum(red, sh);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int c = 0; c < kBlkCols; ++c) part[(size_t)blockIdx.x * kBlkCols + c] = red[c];
+  }
+}
+
+// The scalars of a tile from the workgroups' partials, column by column, each sum in index order as in k_bq_phi (one
+// workgroup): out[v] = {phi, f, c.c, c.ys, |x - xk|^2}_v, phi = f - c.ys + rho/2 c.c + eta/2 |x - xk|^2.  f comes from partF
+// ([nF][kBlkVec], k_bqb_og_pack_sq) when that is given, else from partP[.][v][0]; partP, partE: [nP], [nE][kBlkVec][2].
+__global__ __launch_bounds__(256) void k_bqb_phi(const double* __restrict__ partF, int nF, const double* __restrict__ partP,
+                                                 int nP, const double* __restrict__ partE, int nE, double rho, double eta,
+                                                 double* __restrict__ out) {
+  __shared__ double sh[16];
+  const int cf = (nF + 255) / 256, cp = (nP + 255) / 256, ce = (nE + 255) / 256;
+  for (int v = 0; v < kBlkVec; ++v) {
+    double red[4] = {0.0, 0.0, 0.0, 0.0};
+    if (partF)
+      for (int i = threadIdx.x * cf; i < min(nF, ((int)threadIdx.x + 1) * cf); ++i) red[0] += partF[(size_t)i * kBlkVec + v];
+    for (int i = threadIdx.x * cp; i < min(nP, ((int)threadIdx.x + 1) * cp); ++i) {
+      if (!partF) red[0] += partP[(size_t)i * kBlkCols + 2 * v];
+      red[1] += partP[(size_t)i * kBlkCols + 2 * v + 1];
+    }
+    for (int i = threadIdx.x * ce; i < min(nE, ((int)threadIdx.x + 1) * ce); ++i) {
+      red[2] += partE[(size_t)i * kBlkCols + 2 * v];
+      red[3] += partE[(size_t)i * kBlkCols + 2 * v + 1];
+    }
+    bq_block_sum(red, sh);
+    if (threadIdx.x == 0) {
+      double phi = red[0] - red[2];
+      phi += 0.5 * rho * red[1];
+      phi += 0.5 * eta * red[3];
+      out[v * 5] = phi;
+      out[v * 5 + 1] = red[0];
+      out[v * 5 + 2] = red[1];
+      out[v * 5 + 3] = red[2];
+      out[v * 5 + 4] = red[3];
+    }
+  }
+}
+
 // ---- bordered band (fpsq_band_create_bordered): the s <= kBorderMax rows of A stored LAST couple with every row of M,
 //   M = [B C; C' D],  B = A_b A_b' + delta I (mb x mb, the band the sweeps factor),  C = A_b A_s',  D = A_s A_s' + delta I.
 // A factorisation keeps C and Z = B^-1 C as [.][16] arrays (columns >= s zero) and the Cholesky factor of S = D - C'Z; an

@@ -323,6 +323,25 @@ class DeviceBandEqQP:
         return self._check(self._lib.fpsq_band_solve_two_least_squares_block(
             self._h, k, _lib.ptr(rhs1), _lib.ptr(rhs2), _lib.ptr(p1), _lib.ptr(q1), _lib.ptr(p2), _lib.ptr(q2)))
 
+    def objgrad_block(self, X, GX=None, YS=None, GS=None, XK=None, D=None, B=None):
+        """Row j = objgrad at X[j] on this QP with its linear term replaced by D[j] and its right-hand side by B[j] (None: the
+        model's own d / b for every row): k points of one QP, or a family of QPs that share A and Q, in one pass over the
+        cached factor per 8 rows (include/fpsq.h fpsq_band_qp_objgrad_block).  X, GX, GS, XK, D: (k, n), YS, B: (k, m) float64
+        blocks as in hprod_block; outputs that are None are not produced.  Returns (fx, rc), fx a numpy (k,) array; with
+        rc = 1 (failed factorisation) nothing was evaluated: fx is all nan and the outputs are untouched."""
+        n, m = self.qp.n, self.qp.m
+        k = self._block(X, "X", None, n)
+        for a, name, length in ((GX, "GX", n), (YS, "YS", m), (GS, "GS", n), (XK, "XK", n), (D, "D", n), (B, "B", m)):
+            self._block(a, name, k, length, optional=True)
+        fx = np.full(k, np.nan)
+        if self._factor():
+            return fx, self._fact_rc
+        self._order(X, GX, YS, GS, XK, D, B)
+        self._check(self._lib.fpsq_band_qp_objgrad_block(self._h, self._q, k, _lib.ptr(X), _lib.ptr(D), _lib.ptr(B), self.sigma,
+                                                         self.rho, self.eta, _lib.ptr(XK), fx.ctypes.data, _lib.ptr(GX),
+                                                         _lib.ptr(YS), _lib.ptr(GS)))
+        return fx, 0
+
     def jac_mul(self, trans, alpha, x, beta, y):
         """y = alpha op(A) x + beta y with the model's Jacobian (fpsq_band_jac_mul; trans = 0: A, 1: A')."""
         self._factor()   # (the values reach the handle with a factorisation)

@@ -464,14 +464,28 @@ int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
  *   fpsq_band_qp_hprod_block  column j = fpsq_band_qp_hprod on V[j], for both models (fpsq_band_qp_create, _create_csr);
  *                         hessian_approx 1 and 2 give the same bits, any other value FPSQ_ERR_ARG, as do k < 1, a NULL block
  *                         and V / HV ranges that overlap (message in fpsq_band_last_error).
- * DETERMINISM: a column's result is bitwise independent of k, of the column's position in the block and of what the other
- * columns hold (short tiles are padded with zero columns; every column's sums have a fixed order), and repeatable from call
- * to call.  It is NOT bitwise the single-vector entry's -- the matrix-core sweep sums in another order than the vector-unit
- * sweep --; both meet the same bar against the exact solve. */
+ *   fpsq_band_qp_objgrad_block  column j = fpsq_band_qp_objgrad at X[j], on the model qp (either kind) with its linear term
+ *                         replaced by D[j] and its right-hand side by Bv[j]: a family of QPs that share A and Q -- and so the
+ *                         factor -- but differ in d and b, or k points of one QP.  D: (k, n), NULL = the model's d for every
+ *                         column; Bv: (k, m) in the caller's row order, NULL = the model's b.  So g_j = Q X[j] + d_j,
+ *                         c_j = A X[j] - b_j, and the formulas of fpsq_band_qp_objgrad from there on (the rho and eta terms
+ *                         only when the parameter is positive; XK: (k, n), NULL with eta > 0 means xk = 0).  fx: k doubles
+ *                         on the HOST, required; GX, GS (k, n) and YS (k, m) may be NULL and are then not produced.
+ *                         FPSQ_ERR_ARG (message in fpsq_band_last_error): k < 1, a NULL X or fx, a model of another handle,
+ *                         an output block whose range overlaps an input block or another output block.  The partial sums
+ *                         of the scalars (5 x 2048 x 8 doubles) are allocated at the first call of this entry.
+ * DETERMINISM: a column's result -- fx[j] included -- is bitwise independent of k, of the column's position in the block and
+ * of what the other columns hold (short tiles are padded with zero columns; every column's sums have a fixed order: the
+ * grids depend on the shape alone, per-column partial sums are laid out [workgroup][column] and summed in index order, no
+ * floating-point atomics), and repeatable from call to call.  It is NOT bitwise the single-vector entry's -- the matrix-core
+ * sweep sums in another order than the vector-unit sweep --; both meet the same bar against the exact solve. */
 int fpsq_band_solve_two_least_squares_block(fpsq_band b, int32_t k, const double *rhs1, const double *rhs2, double *p1,
                                             double *q1, double *p2, double *q2);
 int fpsq_band_qp_hprod_block(fpsq_band b, fpsq_band_qp qp, int32_t k, const double *V, double sigma, double rho, double eta,
                              int32_t hessian_approx, double *HV);
+int fpsq_band_qp_objgrad_block(fpsq_band b, fpsq_band_qp qp, int32_t k, const double *X, const double *D, const double *Bv,
+                               double sigma, double rho, double eta, const double *XK, double *fx, double *GX, double *YS,
+                               double *GS);
 
 /* ---- introspection for benchmarks / profiling */
 typedef struct {
