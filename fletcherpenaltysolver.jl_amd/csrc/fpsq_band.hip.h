@@ -1156,7 +1156,9 @@ __global__ __launch_bounds__(256) void k_border_scatter(const int32_t* __restric
 // One workgroup: S = D + delta I - C'Z from the partials of C'Z (k_border_reduce<16> on Z, summed in index order) and the
 // rows mb .. mb + s - 1 of CD = A A_s' (lower triangle), then its Cholesky factor into Ls ([16][16], identity beyond s).
 // Pivots by the rule of wave_diag16: one that is not above tol (0 when no regularisation is set) is replaced by reg (1 when
-// none is set) and counted in info[1] resp. reported in info[0] (first one wins) as stored row mb + j, 1-based.
+// none is set) and counted in info[1] resp. reported in info[0] as stored row mb + j, 1-based.  info[0] keeps the LOWEST stored
+// row, as in wave_diag16: the border rows are stored last and this kernel runs after the band's, so writing only into an empty
+// word (and the first j of this kernel) is that rule.
 __global__ __launch_bounds__(256) void k_border_chol(const double* __restrict__ part, int nparts, const double* __restrict__ CD,
                                                      int mb, int s, double delta, double tol, double reg,
                                                      double* __restrict__ Ls, int* info) {

@@ -277,10 +277,19 @@ __device__ __forceinline__ void wave_diag16(double* L, int LD, int o, int row0, 
       if (r >= rl) *(r == rl ? dinv + o + rl : L + (o + rl) * LD + o + r) = a[r];
   }
   if (lane == 0 && nbad) {
-    if (dyn)
+    if (dyn) {
       atomicAdd(info + 1, nbad);
-    else
-      atomicCAS(info, 0, row0 + o + first);
+    } else {
+      // the LOWEST stored row wins, not the first in time: the two elimination chains of the banded factor run this kernel
+      // side by side on two streams, and the reported row must not depend on which of them got there first
+      const int v = row0 + o + first;
+      int old = atomicCAS(info, 0, v);
+      while (old != 0 && old > v) {
+        const int seen = atomicCAS(info, old, v);
+        if (seen == old) break;
+        old = seen;
+      }
+    }
   }
 }
 

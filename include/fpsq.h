@@ -334,6 +334,12 @@ int fpsq_dense_get_info(fpsq_dense d, fpsq_dense_info *info);
  *                           into 128 x 128 blocks of the band on the device and factors it with a right-looking
  *                           block-banded Cholesky (the dense back-end's MFMA block kernels); returns 1 (soft) with *info
  *                           = first non-positive pivot row when M is not positive definite and no regularisation is set.
+ *                           "First" is by the elimination order, never by time: of several such rows the one at the lowest
+ *                           STORED position is reported (in the caller's numbering), the same one in every factorisation.
+ *                           Without reordering that is the lowest row index.  With two elimination chains the stored order
+ *                           is: rows 0 .. 127, then rows m-1 .. m-128 (descending), then rows 128 .. 255, then rows m-129 ..
+ *                           m-256, ... and the rows left in the middle last -- so of one such row in each chain the one in
+ *                           the block nearer to ITS end of the matrix wins, and at equal block distance the top chain's.
  *   fpsq_band_set_regularization = the dynamic regularisation of :345-348, as for the dense back-end.
  *   fpsq_band_solve_two_*  = `ldiv!` with two right-hand sides (:189-203, :236-251) on the cached factor.
  * Storage is (m / 128) x (half bandwidth in blocks + 1) blocks; create fails with FPSQ_ERR_STATE when that does not fit
