@@ -39,7 +39,7 @@ struct CsrView {
   // cs16 = slot | (col & 31) << 11, cs8 = col >> 5
   const uint16_t* cs16;
   const uint8_t* cs8;
-  // shared values (fpsq.hip pad_blocks): non-null = the blocks hold no values; `vals` is the row-group array of A and
+  // shared values (fpsq_layout.h pad_blocks): non-null = the blocks hold no values; `vals` is the row-group array of A and
   // segdesc[32 L + s] locates the 64 entries of segment s of block L in it (base = blkdesc[L].w)
   const uint4* segdesc;
   int32_t zero_pos;  // an entry of that array that always holds 0.0 (the lanes past a segment's valid entries read it)
@@ -735,7 +735,7 @@ __global__ __launch_bounds__(kBlock) void k_local_allgather(GatherSrc S, double*
   }
 }
 
-// ---- peer-to-peer route of the halo-sharded loop (fpsq.hip: P2PRoute; P2PLocalComm = the shards of ONE process on one GPU,
+// ---- peer-to-peer route of the halo-sharded loop (fpsq_comm.hip.h: P2PRoute; P2PLocalComm = the shards of ONE process on one GPU,
 // IpcComm = the ranks of a node with hipIpc-mapped pointers, the stores then travel over xGMI).  No collective library
 // call: a rank WRITES its record straight into its peers' receive areas, then a sequence number into their flag words, and
 // waits -- in the same small kernel -- until its own flag words carry that number (the guide's "handoff-flag": plain

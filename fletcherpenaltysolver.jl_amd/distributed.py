@@ -13,7 +13,7 @@ slices.  Two layouts of the n-vectors (x, g, gs, gx, p1, p2):
   n-vectors run over the OWNED prefix [w_lo(r), w_lo(r+1)) of each window.
 
 Everything here is host-side planning / slicing / re-assembly; the per-iteration exchanges happen inside libfpsq on the
-solver's stream (RCCL send/recv + all-reduce, csrc/fpsq.hip `comm_reduce_long`).
+solver's stream (RCCL send/recv + all-reduce, csrc/fpsq_launch.hip.h `comm_reduce_long`).
 """
 from __future__ import annotations
 
@@ -138,7 +138,7 @@ def shard_qp_halo(qp, plan: HaloPlan, r: int):
 def halo_exchange_add(vec: np.ndarray, plan: HaloPlan, rank: int, group=None) -> np.ndarray:
     """The halo step of the sharded A' product on HOST arrays: `vec` (window x k) holds this rank's partial products;
     returns vec with the neighbours' partials added on the two overlap regions -- the exchange libfpsq performs on the
-    device with ncclSend/ncclRecv (csrc/fpsq.hip RcclComm::halo_exchange + k_halo_add)."""
+    device with ncclSend/ncclRecv (csrc/fpsq_comm.hip.h RcclComm::halo_exchange + k_halo_add)."""
     import torch
     import torch.distributed as dist
 

@@ -533,7 +533,7 @@ int fpsq_set_profiling(fpsq_handle h, int32_t on);
 
 /* Test hook for the run-ahead heuristics of the Krylov loop.  A solve normally enqueues the iterations of the PREVIOUS call
  * of the same kind without looking at the device and, right behind them, its final vector update and the caller's epilogue
- * kernels gated on the recurrences' `done` flags (csrc/fpsq.hip run_krylov).  This call overrides that expected count for
+ * kernels gated on the recurrences' `done` flags (csrc/fpsq_run.hip.h run_krylov).  This call overrides that expected count for
  * the NEXT solve call of the handle only (expect >= 0; 0 = "unknown": no speculation), so that tests can place the
  * speculation before, at and behind the true iteration count deterministically.  Results never depend on it. */
 int fpsq_debug_expect_iterations(fpsq_handle h, int64_t expect);

@@ -1,5 +1,5 @@
 // loopback_rccl.cpp -- TEST INFRASTRUCTURE, not part of the product: a stand-in for librccl that carries the ten entry
-// points libfpsq.so binds (fpsq.hip: RcclApi) between PROCESSES OF ONE HOST through a shared file mapping (/tmp), so that the
+// points libfpsq.so binds (fpsq_comm.hip.h: RcclApi) between PROCESSES OF ONE HOST through a shared file mapping (/tmp), so that the
 // multi-rank code path (bench.py --gpus N: unique-id broadcast, fpsq_comm_init, all-gathers, grouped send/recv halo
 // exchanges, all-reduces) can be executed for real on a box with ONE GPU -- RCCL itself refuses two ranks on one device.
 // libfpsq.so loads it when FPSQ_RCCL_LIB names it (tests/test_gpu_bench.py).  Semantics: every call synchronises the stream

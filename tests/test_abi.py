@@ -66,6 +66,20 @@ def test_default_options_follow_reference_defaults():
     assert o.kkt_method == 0  # LSQR + CRAIG, the reference's iterative path
 
 
+def test_every_environment_switch_is_documented():
+    """Every FPSQ_* name the library reads with getenv occurs in INTEGRATION.md (its switch table)."""
+    import glob
+
+    csrc = os.path.join(ROOT, "fletcherpenaltysolver.jl_amd", "csrc")
+    names = set()
+    for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
+        names |= set(re.findall(r'getenv\("(FPSQ_[A-Z0-9_]+)"', open(path).read()))
+    assert len(names) >= 40  # (the pattern still finds them)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    documented = set(re.findall(r"FPSQ_[A-Z0-9_]+", doc))
+    assert sorted(names - documented) == []
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
 

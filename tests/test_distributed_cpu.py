@@ -66,7 +66,7 @@ def _sharded_lsqr(local, n, b, lam, iters):
 
 
 def _halo_lsqr(local, plan, rank, b_win, lam, iters):
-    """LSQR on B = A' with n-vectors as COLUMN WINDOWS: the device loop of csrc/fpsq.hip in halo mode, on the host, with
+    """LSQR on B = A' with n-vectors as COLUMN WINDOWS: the device loop of csrc/fpsq_run.hip.h in halo mode, on the host, with
     the collectives of fps_amd.distributed."""
     import scipy.sparse as sp
     from fps_amd.distributed import allreduce_sum, halo_exchange_add

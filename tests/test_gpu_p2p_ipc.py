@@ -1,4 +1,4 @@
-"""The peer-to-peer exchange route BETWEEN PROCESSES (include/fpsq.h fpsq_comm_set_route, csrc/fpsq.hip IpcComm): 2 and 3
+"""The peer-to-peer exchange route BETWEEN PROCESSES (include/fpsq.h fpsq_comm_set_route, csrc/fpsq_comm.hip.h IpcComm): 2 and 3
 ranks, one process each, all on this box's one GPU.  hipIpc handles open between processes that share a device exactly as
 between the GPUs of a node, so everything but the link is exercised: export / all-gather / import of the handles at the first
 solve, the unanimous decision, k_p2p_gather / k_p2p_halo writing into the peers' mapped buffers, sequence flags, bounded

@@ -1152,7 +1152,7 @@ def test_column_sorted_at_blocks_are_bitwise_the_row_order_layout(monkeypatch, d
     blocks in row order (FPSQ_AT_SORTED=0) -- objgrad, hprod (both Hessian approximations), the seam solves, the one-lane
     kernels of an unfused handle, with the scalar steps riding in the products (leader workgroups) and without.
     shared = 1 (the default since round 4): the blocks hold NO values of their own -- every entry is read from the row-group
-    copy of A through segment descriptors (fpsq.hip pad_blocks, "shared values"): the entries stream in another order
+    copy of A through segment descriptors (fpsq_layout.h pad_blocks, "shared values"): the entries stream in another order
     again, into the same LDS slots."""
     qp = _small_pde(seed=13, n=30000, m=3000)
     monkeypatch.setenv("FPSQ_RIDE_LEAD", lead)
@@ -1230,7 +1230,7 @@ def test_a_late_leader_changes_nothing(monkeypatch, late):
     """Sixteen leaders compute the riding steps redundantly and any of them may start late (another kernel holding its XCD).
     The riding UPDATE workgroups of the same launch are released by the record of their own XCC's leader alone, so whatever
     they write must not be an input of the step the late leader is still to compute: the update partials alternate between
-    two arrays (fpsq.hip: pW / pWalt).  FPSQ_DEBUG_RIDE_DELAY=c+1 holds leader c of every launch back by ~100 us -- a
+    two arrays (fpsq_handle.hip.h: pW / pWalt).  FPSQ_DEBUG_RIDE_DELAY=c+1 holds leader c of every launch back by ~100 us -- a
     committing leader (0: lane 0, 8: lane 1) or a publishing-only one -- and every output and statistic of objgrad, hprod
     Val(1) / Val(2), solve_two_mixed and solve_two_extras (the MINRES lane: beta = sqrt of a sum of those partials) must stay
     BITWISE that of a handle with stand-alone step launches (FPSQ_RIDE_LEAD=0)."""
