@@ -718,9 +718,13 @@ int fpo_lnlq_op(const fpo_op *B, const double *b, double delta_reg, double atol,
     sym_givens(epsbar, bhat_n, &c_n, &s_n, &eps_k);
     const double eta_n = ahat_n * s_n;
     const double epsbar_n = -ahat_n * c_n;
-    const double tau_n = -bhat_n * tau / ahat_n;
+    /* Exact breakdown: beta_{k+1} = 0 leaves u_{k+1} = 0 and alpha_{k+1} = 0 -- the bidiagonalisation has ended and the CRAIG
+     * point is the solution (rNorm_cg = 0 below).  There is no v_{k+1} and no wbar_{k+1}: their coefficients are zero, where the
+     * recurrence as it stands forms 0 / 0 and the transfer then writes NaN over a solved system (a Jacobian of one row gets
+     * there in one pass whenever the rounding residue of B v_1 - alpha_1 u_1 happens to be exactly zero). */
+    const double tau_n = ahat_n != 0.0 ? -bhat_n * tau / ahat_n : 0.0;
     const double zeta_k = c_n * zetabar;
-    const double zetabar_n = (tau_n - eta_n * zeta_k) / epsbar_n;
+    const double zetabar_n = epsbar_n != 0.0 ? (tau_n - eta_n * zeta_k) / epsbar_n : 0.0;
     /* (y^L)_{k+1} = (y^L)_k + zeta_k w_k,  w_k = c wbar_k + s u_{k+1};  wbar_{k+1} = s wbar_k - c u_{k+1} */
     axpy(m, zeta_k * c_n, wbar, y);
     axpy(m, zeta_k * s_n, u, y);

@@ -24,58 +24,7 @@ TIGHT = dict(ls_atol=1e-15, ls_rtol=1e-15, ls_axtol=1e-15, ls_btol=1e-15, ls_eto
              ln_atol=1e-15, ln_rtol=1e-15, ln_btol=1e-15, ln_conlim=0.0)
 
 
-class _Handle:
-    """Thin test helper around the raw C ABI for a CSR matrix."""
-
-    def __init__(self, A, delta=0.0, **opts):
-        self.lib = _lib.load()
-        A = sp.csr_matrix(A)
-        self.m, self.n = A.shape
-        o = _lib.Options()
-        self.lib.fpsq_default_options(self.n, self.m, C.byref(o))
-        for k, v in opts.items():
-            setattr(o, k, v)
-        self.h = C.c_void_p()
-        assert self.lib.fpsq_create(C.byref(self.h), self.n, self.m, C.byref(o)) == 0, self.lib.fpsq_last_error(None)
-        rp, ci = A.indptr.astype(np.int32), A.indices.astype(np.int32)
-        assert self.lib.fpsq_set_jacobian_structure_csr(self.h, rp.ctypes.data, ci.ctypes.data) == 0, self.err()
-        v = np.ascontiguousarray(A.data, dtype=np.float64)
-        assert self.lib.fpsq_set_jacobian_values(self.h, v.ctypes.data) == 0, self.err()
-        assert self.lib.fpsq_set_delta(self.h, delta) == 0
-        self.st = (_lib.Stats * 2)()
-
-    def err(self):
-        return self.lib.fpsq_last_error(self.h)
-
-    def jac_mul(self, trans, alpha, x, beta, y):
-        y = np.array(y, dtype=np.float64)
-        x = np.ascontiguousarray(x, dtype=np.float64)
-        assert self.lib.fpsq_jac_mul(self.h, trans, alpha, x.ctypes.data, beta, y.ctypes.data) == 0, self.err()
-        return y
-
-    def two(self, fn, r1, r2, sizes):
-        r1 = np.ascontiguousarray(r1, dtype=np.float64)
-        r2 = np.ascontiguousarray(r2, dtype=np.float64)
-        outs = [np.empty(k) for k in sizes]
-        rc = fn(self.h, r1.ctypes.data, r2.ctypes.data, *[o.ctypes.data for o in outs], self.st)
-        assert rc >= 0, self.err()
-        return (*outs, rc)
-
-    def solve_two_mixed(self, r1, r2):
-        return self.two(self.lib.fpsq_solve_two_mixed, r1, r2, (self.n, self.m, self.n, self.m))
-
-    def solve_two_least_squares(self, r1, r2):
-        return self.two(self.lib.fpsq_solve_two_least_squares, r1, r2, (self.n, self.m, self.n, self.m))
-
-    def solve_two_extras(self, r1, r2):
-        return self.two(self.lib.fpsq_solve_two_extras, r1, r2, (self.m, self.m))
-
-    def close(self):
-        self.lib.fpsq_destroy(self.h)
-
-
-def _rel(a, b):
-    return np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300)
+from abi_handle import _Handle, _rel  # noqa: E402  (tests/abi_handle.py: shared with tests/test_gpu_lane_structures.py)
 
 
 # ---------------------------------------------------------------------------------------------- SpMV
@@ -535,31 +484,34 @@ def test_order_sensitive_structures_converge_to_the_exact_solve(oracle, kind):
     H.close()
 
 
+@pytest.mark.parametrize("ln_method", [0, 1])  # 1: LNLQ as the least-norm recurrence of objgrad (fpsq_options.ln_method)
 @pytest.mark.parametrize("kind", ["tiny", "square-ish", "empty-columns", "dense-row", "dense-column", "wide-window"])
-def test_fused_qp_entries_on_awkward_structures(oracle, kind):
+def test_fused_qp_entries_on_awkward_structures(oracle, kind, ln_method):
     """The fused device entries (fpsq_qp_objgrad / fpsq_qp_hprod: fast start, riding updates and scalar steps, speculative
     tail) on the same shapes, twice per model (first call, then with the run-ahead armed): fx / gx / ys and Hv follow the C
-    restatement of objgrad! / hprod! (1e-4: see the seam test above), same return codes."""
+    restatement of objgrad! / hprod! (1e-4: see the seam test above), same return codes; with CRAIG and with LNLQ (ln_method = 1)
+    as the least-norm recurrence of objgrad."""
     rng = np.random.default_rng(21)
     A = _random_structure(kind, rng)
     A.sort_indices()
     m, n = A.shape
     qp = problems._finish(kind, n, m, A.indptr.astype(np.int64), A.indices.astype(np.int64), np.ascontiguousarray(A.data), 7)
-    dev = DeviceEqQP(qp, sigma=1e3, rho=1.0, delta=0.25)
+    dev = DeviceEqQP(qp, sigma=1e3, rho=1.0, delta=0.25, ln_method=ln_method)
+    opts = oracle.default_options(n, m, ln_method=ln_method)
     v = rng.standard_normal(n)
     for t in range(2):
         x = qp.point(1 + t)
         gx, ys, hv = np.empty(n), np.empty(m), np.empty(n)
         fx, rc = dev.objgrad(x, gx=gx, ys=ys)
-        o = oracle.qp_objgrad(qp, x, 1e3, 1.0, 0.25)
+        o = oracle.qp_objgrad(qp, x, 1e3, 1.0, 0.25, opts=opts)
         assert rc == o["rc"] and abs(fx - o["fx"]) <= 1e-6 * max(1.0, abs(o["fx"]))
         assert _rel(gx, o["gx"]) < 1e-4 and _rel(ys, o["ys"]) < 1e-4
         rch = dev.hprod(v, hv, 2)
-        oh = oracle.qp_hprod(qp, v, 1e3, 1.0, 0.25)
+        oh = oracle.qp_hprod(qp, v, 1e3, 1.0, 0.25, opts=opts)
         assert rch == oh["rc"] and _rel(hv, oh["Hv"]) < 1e-4
         # Val(1): + the LSQR / MINRES lanes of solve_two_extras (their steps ride with leaders too)
         rch = dev.hprod(v, hv, 1)
-        oh = oracle.qp_hprod(qp, v, 1e3, 1.0, 0.25, approx=1)
+        oh = oracle.qp_hprod(qp, v, 1e3, 1.0, 0.25, approx=1, opts=opts)
         assert rch == oh["rc"] and _rel(hv, oh["Hv"]) < 1e-4
     dev.close()
 
