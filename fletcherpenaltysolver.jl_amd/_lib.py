@@ -91,6 +91,7 @@ SYMBOLS = [
     ("fpsq_ys_gs", C.c_int, [_VP, _DP, _DP, _D, _DP, _DP, _DP, _DP, C.POINTER(Stats)]),
     ("fpsq_jac_mul", C.c_int, [_VP, _I32, _D, _DP, _D, _DP]),
     ("fpsq_qp_create", C.c_int, [_VP, _DP, _DP, _DP, C.POINTER(_VP)]),
+    ("fpsq_qp_create_csr", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.POINTER(_VP)]),
     ("fpsq_qp_destroy", C.c_int, [_VP]),
     ("fpsq_qp_objgrad", C.c_int, [_VP, _VP, _DP, _D, _D, _D, _DP, C.POINTER(C.c_double), _DP, _DP, _DP,
                                   C.POINTER(Stats)]),

@@ -42,6 +42,8 @@ thread_local std::string g_create_error;
 #include "fpsq_structure.hip.h"  // uploads of the layouts, workspaces, finish_structure
 #include "fpsq_launch.hip.h"     // product launches, halo_finish, wait_progress
 #include "fpsq_run.hip.h"        // KrylovRun<NL>, run_krylov, run_lanes
+#include "fpsq_qp_csr.hip.h"     // k_qp_csr<LG, MODE>: the products with R of a sparse objective Hessian
+#include "fpsq_qcsr.h"           // the host-side check and split Q = diag(q) + R
 
 namespace {
 
@@ -1109,7 +1111,76 @@ int fpsq_qp_destroy(fpsq_qp qp) {
   return FPSQ_OK;
 }
 
+// the single-GPU LSQR + CRAIG handle is the scope of a model with a sparse objective Hessian: in halo mode the n-vectors are
+// column windows and R would need an exchange of its own; MINRES on K keeps its vectors interleaved
+static int sparse_q_scope(fpsq_handle h, const char* who) {
+  if (!h->comm && h->opt.kkt_method == FPSQ_KKT_LSQR_CRAIG) return FPSQ_OK;
+  h->err = std::string(who) + ": a sparse objective Hessian needs a single-GPU handle with kkt_method = FPSQ_KKT_LSQR_CRAIG (this one " +
+           (h->comm ? "has a communicator)" : "runs MINRES on K)");
+  return FPSQ_ERR_STATE;
+}
+
+int fpsq_qp_create_csr(fpsq_handle h, const int32_t* q_rowptr, const int32_t* q_colind, const double* q_vals, const double* d,
+                       const double* b, fpsq_qp* out) {
+  if (!h || !q_rowptr || !d || !b || !out) return FPSQ_ERR_ARG;
+  if (int rc = sparse_q_scope(h, "qp_create_csr")) return rc;
+  hipSetDevice(h->opt.device);
+  const int64_t n = h->n;
+  auto bad = [&](const std::string& what) {
+    h->err = "qp_create_csr: " + what;
+    return FPSQ_ERR_ARG;
+  };
+  if (n >= INT32_MAX) return bad("n does not fit the 32-bit row indices of Q");
+  // Q on the host, once: the checks and the split Q = diag(q) + R  (fpsq_qcsr.h)
+  std::vector<int32_t> rp((size_t)n + 1);
+  HIPCHK(h, hipMemcpy(rp.data(), q_rowptr, ((size_t)n + 1) * 4, hipMemcpyDefault));
+  if (const std::string what = qcsr_check_rowptr(n, rp.data()); !what.empty()) return bad(what);
+  const size_t nnz = (size_t)rp[n];  // (32-bit offsets: nnz(R) <= nnz(Q) < 2^31)
+  if (nnz && (!q_colind || !q_vals)) return FPSQ_ERR_ARG;
+  std::vector<int32_t> ci(nnz);
+  std::vector<double> va(nnz);
+  if (nnz) {
+    HIPCHK(h, hipMemcpy(ci.data(), q_colind, nnz * 4, hipMemcpyDefault));
+    HIPCHK(h, hipMemcpy(va.data(), q_vals, nnz * 8, hipMemcpyDefault));
+  }
+  QcsrSplit sp;
+  if (const std::string what = qcsr_check_split(n, rp.data(), ci.data(), va.data(), sp); !what.empty()) return bad(what);
+  fpsq_qp qp = nullptr;
+  if (int rc = fpsq_qp_create(h, sp.qd.data(), d, b, &qp)) return rc;
+  const size_t rnz = sp.rci.size();
+  if (dalloc(h, &qp->r_rowptr, (size_t)n + 1) || dalloc(h, &qp->r_colind, rnz) || dalloc(h, &qp->r_vals, rnz) ||
+      dalloc(h, &qp->d_eff, (size_t)n) || dalloc(h, &qp->tail, (size_t)n)) {
+    delete qp;
+    return FPSQ_ERR_HIP;
+  }
+  if (hipMemcpy(qp->r_rowptr, sp.rrp.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      (rnz && (hipMemcpy(qp->r_colind, sp.rci.data(), rnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
+               hipMemcpy(qp->r_vals, sp.rv.data(), rnz * 8, hipMemcpyHostToDevice) != hipSuccess))) {
+    h->err = "qp_create_csr: cannot upload the objective Hessian";
+    delete qp;
+    return FPSQ_ERR_HIP;
+  }
+  qp->lgR = lane_group((int64_t)rnz, n);
+  const int64_t tiles = std::max<int64_t>(1, (n + kBlock / qp->lgR - 1) / (kBlock / qp->lgR));
+  qp->gridF = (int)std::min<int64_t>(tiles, kEwBlocksMax);      // (pQ holds 2 kEwBlocksMax partials: the start-up's, then these)
+  qp->gridR = (int)std::min<int64_t>(tiles, 2 * kEwBlocksMax);  // (256 CUs x 8 resident workgroups of 256 threads)
+  *out = qp;
+  return FPSQ_OK;
+}
+
 }  // extern "C"
+
+namespace {
+// one launch of the row-product kernel on R of a model with a sparse objective Hessian
+template <int MODE>
+void launch_qp_csr(fpsq_handle h, fpsq_qp qp, const double* a, const double* b, const double* in, double* out, double* pf, double* pz,
+                   Gates gates = Gates{}) {
+  QrArgs A{qp->r_rowptr, qp->r_colind, qp->r_vals, a, b, in, out, pf, pz, (int32_t)h->n};
+  const int grid = MODE == QR_FRONT ? qp->gridF : qp->gridR;
+  WITH_LANE_GROUP(qp->lgR, hipLaunchKernelGGL((k_qp_csr<LG, MODE>), dim3(grid), dim3(kBlock), 0, h->stream, A, gates.c0, gates.c1));
+  if (MODE != QR_HSV) h->launches++;  // (QR_HSV stands in for k_qp_hsv, which the epilogue of hprod counts)
+}
+}  // namespace
 
 namespace {
 // stand-alone form of qp_fx (sharded runs: the m-vector sums pass through an all-reduce first)
@@ -1137,6 +1208,9 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
     h->err = "qp_objgrad: bad argument";
     return FPSQ_ERR_ARG;
   }
+  const bool sparse_q = qp->r_rowptr != nullptr;  // Q = diag(q) + R (fpsq_qp_create_csr): two launches more, fpsq_qp_csr.hip.h
+  if (sparse_q)
+    if (int rc = sparse_q_scope(h, "qp_objgrad")) return rc;
   hipSetDevice(h->opt.device);
   hipStream_t s = h->stream;
   order_inputs(h);
@@ -1164,8 +1238,13 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
   const bool local_vec = !h->comm || h->halo;  // single GPU, or row-sharded with column windows (halo mode)
   const bool fast = local_vec && h->opt.fuse_two_rhs != 0 && h->opt.kkt_method == FPSQ_KKT_LSQR_CRAIG;
   RunRequest req;
+  // sparse Q, in front: d_eff = d + R x and the partials of -1/2 x'R x behind the gn partials of f (zeros behind those of
+  // ||x - xk||^2): the gradient body below then forms g = q.*x + d_eff = Q x + d and sums f + 1/2 x'R x, unchanged
+  const int gr = sparse_q ? qp->gridF : 0;
+  if (sparse_q) launch_qp_csr<QR_FRONT>(h, qp, dx, nullptr, qp->d, qp->d_eff, h->pQ[0] + gn, h->pQ[1] + gn);
+  double* tgx = sparse_q ? qp->tail : dgx;  // (the tail's gx: the gated launch behind it writes dgx = tgx - R p2)
   {
-    QpGradArgs qg{qp->q, qp->d, dx, dxk, h->g, n, h->pQ[0], h->pQ[1], fast ? h->LP : (double*)nullptr,
+    QpGradArgs qg{qp->q, sparse_q ? qp->d_eff : qp->d, dx, dxk, h->g, n, h->pQ[0], h->pQ[1], fast ? h->LP : (double*)nullptr,
                   fast ? h->pE : (double*)nullptr, n_owned(h), gn};
     if (fast && !(h->ab_mask & 1)) {
       req.startup_qg = qg;  // evaluated by the start-up launch of the recurrences (k_startup): no launch of its own
@@ -1197,7 +1276,7 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
     fa.seq = seq;
     fa.pf = h->pQ[0];
     fa.pdx = h->pQ[1];
-    fa.np_n = gn;
+    fa.np_n = gn + gr;
     fa.pcy = h->pC[0];
     fa.pcc = h->pC[1];
     fa.np_m = gm;
@@ -1246,7 +1325,7 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
         ge.rho = rho;
         ge.eta = eta;
         ge.gs = h->gs;
-        ge.gx = dgx;
+        ge.gx = tgx;
         ge.fx = grad_fx ? fa : none;
         one_launch = launch_at_tail<2>(h, h->SP, h->LP, ge, t.gates);
       }
@@ -1264,7 +1343,7 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
         if (h->halo)
           if (int rc = halo_finish<2>(h, nullptr, h->LP, h->ctl_raw, h->ctl_raw, nullptr, t.gates)) return rc;
         hipLaunchKernelGGL(k_qp_penalty_grad, dim3(grad_fx ? gn + 1 : gn), dim3(kBlock), 0, s, (const double*)nullptr, h->g, h->LP,
-                           h->Cx, qp->q, (const double*)nullptr, dx, dxk, sigma, rho, eta, h->gs, dgx, n, grad_fx ? fa : none,
+                           h->Cx, qp->q, (const double*)nullptr, dx, dxk, sigma, rho, eta, h->gs, tgx, n, grad_fx ? fa : none,
                            t.gates.c0, t.gates.c1);
         h->launches++;
       }
@@ -1272,10 +1351,13 @@ static int impl_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double* x, double si
       if (rho > 0.0)
         if (int rc = at_product_const(h, 1.0, h->c, 0.0, nullptr, h->jc, t.gates)) return rc;  // J'c   (:424-428)
       hipLaunchKernelGGL(k_qp_penalty_grad, dim3(in_launch ? gn + 1 : gn), dim3(kBlock), 0, s, h->p1, h->g,
-                         (const double*)nullptr, h->Cx, qp->q, h->jc, dx, dxk, sigma, rho, eta, h->gs, dgx, n,
+                         (const double*)nullptr, h->Cx, qp->q, h->jc, dx, dxk, sigma, rho, eta, h->gs, tgx, n,
                          in_launch ? fa : none, t.gates.c0, t.gates.c1);
       h->launches++;
     }
+    // sparse Q, behind whichever tail ran (p2 = v is in h->Cx after each of them): gx = tgx - R p2, gated like the tail.  Out of
+    // place, so an epilogue that is enqueued twice writes the same bytes twice
+    if (sparse_q) launch_qp_csr<QR_SUB>(h, qp, h->Cx, nullptr, tgx, dgx, nullptr, nullptr, t.gates);
     if (!in_launch) {  // phi: c'ys and c'c are sums over the rank's rows only
       PresumArgs P{};
       P.p[0] = fa.pcy;
@@ -1351,6 +1433,9 @@ static int impl_qp_hprod(fpsq_handle h, fpsq_qp qp, const double* v, double sigm
     h->err = "qp_hprod: bad argument (hessian_approx is 1 or 2)";
     return FPSQ_ERR_ARG;
   }
+  const bool sparse_q = qp->r_rowptr != nullptr;  // Q = diag(q) + R (fpsq_qp_create_csr): one launch more, fpsq_qp_csr.hip.h
+  if (sparse_q)
+    if (int rc = sparse_q_scope(h, "qp_hprod")) return rc;
   hipSetDevice(h->opt.device);
   hipStream_t s = h->stream;
   order_inputs(h);
@@ -1365,7 +1450,12 @@ static int impl_qp_hprod(fpsq_handle h, fpsq_qp qp, const double* v, double sigm
   double* dhv = on_this_device(h, Hv) ? Hv : h->gx;
   bool lsq_repeats = false;
   call_begin(h);
-  hipLaunchKernelGGL(k_qp_hsv, dim3(gn), dim3(kBlock), 0, s, qp->q, dv, h->in_n2, n);                    // :537
+  double* thv = sparse_q ? qp->tail : dhv;  // (the tail's Hv: the gated launch behind it writes dhv = thv - R (v - p1))
+  if (sparse_q) {
+    launch_qp_csr<QR_HSV>(h, qp, dv, nullptr, qp->q, h->in_n2, nullptr, nullptr);  // Hsv = q .* v + R v = Q v            :537
+  } else {
+    hipLaunchKernelGGL(k_qp_hsv, dim3(gn), dim3(kBlock), 0, s, qp->q, dv, h->in_n2, n);                  // :537
+  }
   TailFn epi = [&](const TailCtx& t) -> int {
     bool fin_done = false;
     if (rho > 0.0) {                                                                                      // :557-558
@@ -1380,18 +1470,20 @@ static int impl_qp_hprod(fpsq_handle h, fpsq_qp qp, const double* v, double sigm
         ge.sigma = sigma;
         ge.rho = rho;
         ge.eta = eta;
-        ge.hv = dhv;
+        ge.hv = thv;
         fin_done = launch_at_tail<1>(h, h->in_m, h->jc, ge, t.gates);
       }
       if (!fin_done)
         if (int rc = at_product_const(h, 1.0, h->in_m, 0.0, nullptr, h->jc, t.gates)) return rc;
     }
     if (!fin_done) {
-      hipLaunchKernelGGL(k_qp_hprod_fin, dim3(gn), dim3(kBlock), 0, s, h->p1, h->p2b, qp->q, dv, h->jc, sigma, rho, eta, dhv,
+      hipLaunchKernelGGL(k_qp_hprod_fin, dim3(gn), dim3(kBlock), 0, s, h->p1, h->p2b, qp->q, dv, h->jc, sigma, rho, eta, thv,
                          n, t.gates.c0, t.gates.c1);                                                      // :543-562
       h->launches++;
     }
     h->launches++;
+    // sparse Q: Hv = thv - R (v - p1), gated like the tail and out of place like objgrad's
+    if (sparse_q) launch_qp_csr<QR_SUB>(h, qp, dv, h->p1, thv, dhv, nullptr, nullptr, t.gates);
     return 0;
   };
   const bool local_vec = !h->comm || h->halo;

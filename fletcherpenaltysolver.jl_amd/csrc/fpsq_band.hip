@@ -2,6 +2,7 @@
 // (ordering, two elimination chains), the block-banded factorisation and the solves, the device-resident eq-QP model
 // (fpsq_band_qp_*) and the block entries.
 #include "fpsq_band.hip.h"
+#include "fpsq_qcsr.h"
 
 using namespace fpsq;
 using namespace fpsq_direct;
@@ -1045,12 +1046,10 @@ int fpsq_band_qp_create_csr(fpsq_band b, const int32_t* q_rowptr, const int32_t*
     return FPSQ_ERR_ARG;
   };
   // Q on the host, once: the checks (the kernels read rows only, so an unsymmetric Q would give a wrong Hessian silently)
-  // and the split Q = diag(q) + R
+  // and the split Q = diag(q) + R  (fpsq_qcsr.h)
   std::vector<int32_t> rp((size_t)n + 1);
   CHK(b, hipMemcpy(rp.data(), q_rowptr, ((size_t)n + 1) * 4, hipMemcpyDefault));
-  if (rp[0] != 0) return bad("rowptr[0] must be 0");
-  for (int64_t i = 0; i < n; ++i)
-    if (rp[i + 1] < rp[i]) return bad("rowptr decreases at row " + std::to_string(i));
+  if (const std::string what = qcsr_check_rowptr(n, rp.data()); !what.empty()) return bad(what);
   const size_t nnz = (size_t)rp[n];
   if (nnz && (!q_colind || !q_vals)) return FPSQ_ERR_ARG;
   std::vector<int32_t> ci(nnz);
@@ -1059,43 +1058,10 @@ int fpsq_band_qp_create_csr(fpsq_band b, const int32_t* q_rowptr, const int32_t*
     CHK(b, hipMemcpy(ci.data(), q_colind, nnz * 4, hipMemcpyDefault));
     CHK(b, hipMemcpy(va.data(), q_vals, nnz * 8, hipMemcpyDefault));
   }
-  std::vector<std::pair<int32_t, double>> ent(nnz);  // every row sorted by column
-  for (int64_t i = 0; i < n; ++i) {
-    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
-      if (ci[k] < 0 || ci[k] >= n)
-        return bad("column " + std::to_string(ci[k]) + " of row " + std::to_string(i) + " is out of range");
-      ent[k] = {ci[k], va[k]};
-    }
-    std::sort(ent.begin() + rp[i], ent.begin() + rp[i + 1],
-              [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& c) { return a.first < c.first; });
-    for (int32_t k = rp[i] + 1; k < rp[i + 1]; ++k)
-      if (ent[k].first == ent[k - 1].first)
-        return bad("duplicate entry (" + std::to_string(i) + ", " + std::to_string(ent[k].first) + ")");
-  }
-  std::vector<double> qd((size_t)n, 0.0), rv;
-  std::vector<int32_t> rrp((size_t)n + 1, 0), rci;
-  rv.reserve(nnz);
-  rci.reserve(nnz);
-  for (int64_t i = 0; i < n; ++i) {
-    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
-      const int32_t j = ent[k].first;
-      if (j == i) {
-        qd[i] = ent[k].second;
-        continue;
-      }
-      const auto lo = ent.begin() + rp[j], hi = ent.begin() + rp[j + 1];
-      const auto it = std::lower_bound(lo, hi, (int32_t)i,
-                                       [](const std::pair<int32_t, double>& a, int32_t col) { return a.first < col; });
-      if (it == hi || it->first != i)
-        return bad("the pattern is not symmetric: (" + std::to_string(i) + ", " + std::to_string(j) + ") has no transpose");
-      if (!(it->second == ent[k].second))
-        return bad("the values are not symmetric: Q(" + std::to_string(i) + ", " + std::to_string(j) + ") != Q(" +
-                   std::to_string(j) + ", " + std::to_string(i) + ")");
-      rci.push_back(j);
-      rv.push_back(ent[k].second);
-    }
-    rrp[i + 1] = (int32_t)rci.size();
-  }
+  QcsrSplit sp;
+  if (const std::string what = qcsr_check_split(n, rp.data(), ci.data(), va.data(), sp); !what.empty()) return bad(what);
+  const std::vector<double>&qd = sp.qd, &rv = sp.rv;
+  const std::vector<int32_t>&rrp = sp.rrp, &rci = sp.rci;
   fpsq_band_qp qp = nullptr;
   if (int rc = fpsq_band_qp_create(b, qd.data(), d, bvec, &qp)) return rc;
   const size_t rnz = rci.size();

@@ -9,6 +9,7 @@
 // reference: the LDLtSolver path, src/solve_linear_system.jl:206-252.
 #pragma once
 #include "../../include/fpsq.h"
+#include "fpsq_lanegroup.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -1347,25 +1348,7 @@ inline int eval_end(DirectCore* c, int nscal, double* solve_ms, const char* expi
   return call_end(c, expired, solve_ms);
 }
 
-// lanes that share a row in the product kernels of the evaluations: the largest power of two <= the mean row length, 1 .. 64
-inline int lane_group(int64_t nnz, int64_t rows) {
-  const int64_t mean = rows > 0 ? nnz / rows : 1;
-  int lg = 1;
-  while (lg < 64 && 2 * lg <= mean) lg *= 2;
-  return lg;
-}
-
-// runs the statement(s) with the compile-time constant LG = lg (a value lane_group returns)
-#define WITH_LANE_GROUP(lg, ...)                            \
-  switch (lg) {                                             \
-    case 1: { constexpr int LG = 1; __VA_ARGS__; } break;    \
-    case 2: { constexpr int LG = 2; __VA_ARGS__; } break;    \
-    case 4: { constexpr int LG = 4; __VA_ARGS__; } break;    \
-    case 8: { constexpr int LG = 8; __VA_ARGS__; } break;    \
-    case 16: { constexpr int LG = 16; __VA_ARGS__; } break;  \
-    case 32: { constexpr int LG = 32; __VA_ARGS__; } break;  \
-    default: { constexpr int LG = 64; __VA_ARGS__; } break;  \
-  }
+// lane_group(nnz, rows) and WITH_LANE_GROUP(lg, ...): fpsq_lanegroup.h (shared with the iterative handle's sparse Hessian)
 
 // ... and with the compile-time constant NAME = the run-time bool `cond`
 #define WITH_BOOL(cond, NAME, ...)                   \

@@ -328,6 +328,12 @@ static void read_switches(fpsq_handle h) {
 struct fpsq_qp_s {
   fpsq_handle h;
   double *q, *d, *b;
+  // fpsq_qp_create_csr only (r_rowptr != null): Q = diag(q) + R, R in CSR with sorted rows; d_eff = d + R x of the current
+  // objgrad; `tail`: where the tail writes gx / Hv for the gated launch behind it to subtract R p2 / R (v - p1) from
+  int32_t *r_rowptr = nullptr, *r_colind = nullptr;
+  double *r_vals = nullptr, *d_eff = nullptr, *tail = nullptr;
+  int lgR = 1;             // lanes per row of R (lane_group)
+  int gridF = 1, gridR = 1;  // workgroups of the front launch of objgrad (its partials share pQ with the start-up's) / of the others
 };
 
 namespace {

@@ -24,11 +24,18 @@ class DeviceEqQP:
     ROUTES = {"auto": 0, "rccl": 1, "p2p": 2}
     ROUTE_NAMES = {0: "single GPU", 1: "rccl", 2: "p2p-ipc", 3: "local", 4: "local-p2p"}
 
+    sparse_hessian = False   # (DeviceSparseHessianEqQP: a QP that carries hess_* is created with fpsq_qp_create_csr)
+
     def __init__(self, qp, sigma=1e3, rho=1.0, delta=0.0, eta=0.0, device=0, comm=None, halo=None, comm_route=None,
                  **opt_overrides):
-        if getattr(qp, "hess_vals", None) is not None:   # fpsq_qp_* know diag(q) alone: never evaluate the diagonal part silently
+        sparse = getattr(qp, "hess_vals", None) is not None
+        if sparse and not self.sparse_hessian:   # fpsq_qp_create knows diag(q) alone: never evaluate the diagonal part silently
             raise ValueError("DeviceEqQP (the iterative back-end) takes a diagonal objective Hessian only; a QP with a "
-                             "sparse Hessian (EqQP.hess_vals) runs on DeviceBandEqQP")
+                             "sparse Hessian (EqQP.hess_vals) runs on DeviceBandEqQP or, on the iterative back-end, on "
+                             "DeviceSparseHessianEqQP")
+        if self.sparse_hessian and (comm is not None or halo is not None):
+            raise ValueError("DeviceSparseHessianEqQP is single-GPU: comm / halo are not supported (in halo mode the n-vectors "
+                             "are column windows, and the products with the Hessian would need an exchange of their own)")
         self._lib = _lib.load()
         self.qp, self.sigma, self.rho, self.delta, self.eta = qp, sigma, rho, delta, eta
         opts = _lib.Options()
@@ -48,7 +55,14 @@ class DeviceEqQP:
         self._check(self._lib.fpsq_set_jacobian_values(h, np.ascontiguousarray(qp.vals).ctypes.data))
         self._check(self._lib.fpsq_set_delta(h, float(delta)))
         q = C.c_void_p()
-        self._check(self._lib.fpsq_qp_create(h, qp.qdiag.ctypes.data, qp.d.ctypes.data, qp.b.ctypes.data, C.byref(q)))
+        if sparse:   # sparse symmetric Q (full storage): fpsq_qp_create_csr
+            hrp = np.ascontiguousarray(qp.hess_rowptr, dtype=np.int32)
+            hci = np.ascontiguousarray(qp.hess_colind, dtype=np.int32)
+            hv = np.ascontiguousarray(qp.hess_vals, dtype=np.float64)
+            self._check(self._lib.fpsq_qp_create_csr(h, hrp.ctypes.data, hci.ctypes.data, hv.ctypes.data, qp.d.ctypes.data,
+                                                     qp.b.ctypes.data, C.byref(q)))
+        else:
+            self._check(self._lib.fpsq_qp_create(h, qp.qdiag.ctypes.data, qp.d.ctypes.data, qp.b.ctypes.data, C.byref(q)))
         self._q = q
         self.stats = (_lib.Stats * 2)()
         self.stats4 = (_lib.Stats * 4)()   # hprod with hessian_approx = 1: + the two recurrences of solve_two_extras
@@ -166,6 +180,15 @@ class DeviceEqQP:
             self.close()
         except Exception:
             pass
+
+
+class DeviceSparseHessianEqQP(DeviceEqQP):
+    """DeviceEqQP for a QP with a sparse symmetric objective Hessian (`EqQP.hess_*`, `problems.with_sparse_hessian`): the model
+    is created with `fpsq_qp_create_csr` and evaluated with that Hessian -- an objgrad is two launches longer than on the
+    diagonal model, an hprod one (include/fpsq.h).  A QP without `hess_vals` gives the diagonal model.  Single GPU, LSQR + CRAIG /
+    LNLQ only: `comm` / `halo` raise ValueError.  Everything else is DeviceEqQP's surface; `fps_solve_device` takes it as it is."""
+
+    sparse_hessian = True
 
 
 class DeviceBandEqQP:

@@ -215,6 +215,28 @@ int fpsq_qp_objgrad(fpsq_handle h, fpsq_qp qp, const double *x, double sigma, do
  * The Hessian-free sub-solvers call this once per inner CG iteration. */
 int fpsq_qp_hprod(fpsq_handle h, fpsq_qp qp, const double *v, double sigma, double rho, double eta, int32_t hessian_approx,
                   double *Hv, fpsq_stats *st);
+/* The same model with a SPARSE SYMMETRIC objective Hessian, f(x) = 1/2 x'Q x + d'x (a mass or stiffness matrix), on the
+ * iterative handle -- the contract of fpsq_band_qp_create_csr (below): Q is n x n in CSR, 0-based, FULL symmetric storage
+ * (both triangles), columns in any order, the diagonal may be absent (= 0); host or device pointers.  The constraints are
+ * linear, so the Lagrangian Hessian is Q and the two evaluations become (:403-437, :521-570)
+ *   objgrad: g = Q x + d, gx = gs - Q p2 + sigma p2 + rho A'c + eta (x - xk), *fx with f = 1/2 x'Q x + d'x;
+ *   hprod:   (p1, _, p2, _) = solve_two_least_squares(v, Q v), Hv = p2 - Q Ptv + 2 sigma Ptv + rho A'(A v) + eta v;
+ *            hessian_approx = 1 runs its solve_two_extras lanes on (v, 0) as above (nothing in them involves Q).
+ * Checked once, on the host: an index out of range, a duplicate entry, a pattern or values that are not symmetric
+ * (Q_ij != Q_ji) give FPSQ_ERR_ARG and a message in fpsq_last_error(h) that starts with "qp_create_csr:" and names the
+ * range / duplicate / pattern / values -- the kernels read rows only, so an unsymmetric Q would otherwise give a wrong
+ * Hessian silently.  *out is written on success only.
+ * fpsq_qp_objgrad / fpsq_qp_hprod / fpsq_qp_destroy take the object unchanged.  Q = diag(q) + R: the kernels of the Krylov
+ * loop and of its tail run as on the diagonal model, with the diagonal part; R enters in launches of its own -- an objgrad
+ * is two launches longer (d + R x and the -1/2 x'R x partials in front, gx -= R p2 behind the tail), an hprod one
+ * (Q v in front instead of q .* v, Hv -= R (v - p1) behind the tail); every sum in a fixed order, so two calls with the
+ * same arguments return the same bits, and the stream-ordered return (fpsq_set_output_ordering) applies unchanged.  Hv must
+ * not alias v.  Models of either kind may share a handle and do not disturb each other.
+ * SCOPE: single-GPU handles with kkt_method = FPSQ_KKT_LSQR_CRAIG (ln_method CRAIG or LNLQ).  On a handle with a
+ * communicator, or with FPSQ_KKT_MINRES_K, this entry and an evaluation of such a model return FPSQ_ERR_STATE with a
+ * message (in halo mode the n-vectors are column windows: R would need an exchange of its own). */
+int fpsq_qp_create_csr(fpsq_handle h, const int32_t *q_rowptr, const int32_t *q_colind, const double *q_vals,
+                       const double *d, const double *b, fpsq_qp *out);
 
 /* ---- multi-GPU: 1-D row sharding of A across ranks.  Each rank creates its handle with
  * the GLOBAL n and its LOCAL m (its block of constraints), passes its local rows to set_jacobian_*, and
