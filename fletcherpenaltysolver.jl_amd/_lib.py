@@ -65,7 +65,8 @@ class BandInfo(C.Structure):
     _fields_ = [("n", C.c_int64), ("m", C.c_int64), ("nnz", C.c_int64), ("nblocks", C.c_int64),
                 ("bandwidth_blocks", C.c_int64), ("factor_bytes", C.c_int64), ("last_form_ms", C.c_double),
                 ("last_chol_ms", C.c_double), ("last_solve_ms", C.c_double), ("regularized_pivots", C.c_int64),
-                ("reordered", C.c_int64), ("chains", C.c_int64), ("border_rows", C.c_int64), ("last_border_ms", C.c_double)]
+                ("reordered", C.c_int64), ("chains", C.c_int64), ("border_rows", C.c_int64), ("last_border_ms", C.c_double),
+                ("border_cols", C.c_int64), ("border_pivot_ratio", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -123,6 +124,9 @@ SYMBOLS = [
     ("fpsq_band_create_bordered", C.c_int, [C.POINTER(_VP), _I64, _I64, _DP, _DP, _I32, _I32]),
     ("fpsq_band_create_coo_bordered", C.c_int, [C.POINTER(_VP), _I64, _I64, _I64, _DP, _DP, _I32, _I32, _I32]),
     ("fpsq_band_analyze_bordered", C.c_int, [_I64, _I64, _DP, _DP, _I32, _DP, C.POINTER(BandInfo)]),
+    ("fpsq_band_create_bordered_cols", C.c_int, [C.POINTER(_VP), _I64, _I64, _DP, _DP, _I32, _I32, _I32]),
+    ("fpsq_band_create_coo_bordered_cols", C.c_int, [C.POINTER(_VP), _I64, _I64, _I64, _DP, _DP, _I32, _I32, _I32, _I32]),
+    ("fpsq_band_analyze_bordered_cols", C.c_int, [_I64, _I64, _DP, _DP, _I32, _I32, _DP, _DP, C.POINTER(BandInfo)]),
     ("fpsq_band_destroy", C.c_int, [_VP]),
     ("fpsq_band_last_error", C.c_char_p, [_VP]),
     ("fpsq_band_set_regularization", C.c_int, [_VP, _D, _D]),

@@ -49,6 +49,19 @@ struct fpsq_band_s : DirectCore {
   double *bd_c = nullptr, *bd_z = nullptr, *bd_l = nullptr, *bd_part = nullptr, *bd_t = nullptr;
   int bd_grid = 1;
   hipEvent_t evS0 = nullptr, evS1 = nullptr;  // around the border's share of a factorisation (last_border_ms)
+  // long columns (fpsq_band_create_bordered_cols; kernels and algebra: fpsq_band.hip.h "long columns"): `cols` columns of A are
+  // kept out of the band.  bd_c / bd_z hold U and Z = B^-1 U, bd_l the factor of S, bd_part the partials; vrows = 16 bd_grid
+  // virtual rows lie behind row mpad of r2, r16, bd_keep and blk_keep.  t_nnz: entries of the transposed structure (a long
+  // column has bd_grid of them, of value vals[nnz] = 1).  lc_*: the entries of the long columns, column by column (stored
+  // row, stored entry).  bd_keep: the `keep` operand of an evaluation, resp. the x of a transposed product, [mpad + vrows].
+  // bd_t[256]: (largest / smallest pivot of S)^2.  fb_*: the CSR of A_b alone for k_band_form (form_gen = 1), fb_perm its
+  // entries among the stored ones
+  int cols = 0;
+  int64_t t_nnz = 0, fb_nnz = 0;
+  int32_t *lc_ptr = nullptr, *lc_row = nullptr, *lc_ent = nullptr;
+  double* bd_keep = nullptr;
+  int32_t *fb_rowptr = nullptr, *fb_colind = nullptr, *fb_perm = nullptr;
+  double* fb_vals = nullptr;
   fpsq_band_info info{};
 };
 
@@ -332,6 +345,76 @@ std::string band_order(int64_t n, int64_t m, std::vector<int32_t>& rp, std::vect
   return msg;
 }
 
+// The ordering with at most max_cols LONG COLUMNS taken out (include/fpsq.h, "LONG COLUMNS", has the rule): first the ordering
+// of the rows on all columns, as band_order_rows leaves it; then, candidates being the max_cols columns with the most entries
+// (ties: the lower column first), the shortest prefix of them after whose removal no row is empty and band_order_rows orders
+// the rows into a band at most a quarter as wide (in blocks).  If there is one, the result is THAT ordering of the rows, every
+// row with all its entries (the long columns' included, columns are not renumbered), and lcols lists the columns ascending;
+// else the result is the ordering on all columns and lcols is empty.
+std::string band_order_cols(int64_t n, int64_t m, std::vector<int32_t>& rp, std::vector<int32_t>& ci,
+                            std::vector<int32_t>& rperm_h, std::vector<int32_t>& vperm_h, int& chain_safe, int& chain_bw,
+                            int max_cols, std::vector<int32_t>& lcols) {
+  lcols.clear();
+  const std::vector<int32_t> rp0 = rp, ci0 = ci;
+  const std::string msg = band_order_rows(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw);
+  if (!msg.empty() || max_cols <= 0 || m < 2 || n < 2) return msg;
+  const int64_t bwb0 = band_blocks(n, m, rp, ci);
+  if (bwb0 == 0) return msg;
+  const int64_t nnz = rp0[m];
+  std::vector<int64_t> cnt(n, 0);
+  for (int64_t k = 0; k < nnz; ++k) cnt[ci0[k]]++;
+  std::vector<int32_t> cand(n);
+  for (int64_t c = 0; c < n; ++c) cand[c] = (int32_t)c;
+  const int64_t ncand = std::min<int64_t>(max_cols, n - 1);
+  std::partial_sort(cand.begin(), cand.begin() + ncand, cand.end(),
+                    [&](int32_t a, int32_t b) { return cnt[a] != cnt[b] ? cnt[a] > cnt[b] : a < b; });
+  std::vector<char> out(n, 0);
+  for (int64_t k = 1; k <= ncand; ++k) {
+    out[cand[k - 1]] = 1;
+    std::vector<int32_t> rp_b(1, 0), ci_b;  // the rows on the remaining columns, in the caller's order
+    bool empty_row = false;
+    for (int64_t i = 0; i < m && !empty_row; ++i) {
+      for (int32_t t = rp0[i]; t < rp0[i + 1]; ++t)
+        if (!out[ci0[t]]) ci_b.push_back(ci0[t]);
+      empty_row = (int32_t)ci_b.size() == rp_b.back();
+      rp_b.push_back((int32_t)ci_b.size());
+    }
+    if (empty_row) break;  // rule (a); a longer prefix empties the same row
+    ci_b.resize(std::max<size_t>(ci_b.size(), 1));
+    std::vector<int32_t> rperm_b, vperm_b;
+    int cs = 0, cb = 0;
+    if (!band_order_rows(n, m, rp_b, ci_b, rperm_b, vperm_b, cs, cb).empty()) break;
+    if (4 * band_blocks(n, m, rp_b, ci_b) > bwb0) continue;
+    // taken: the rows in that order, each with all its entries
+    if (rperm_b.empty()) {
+      rp = rp0;
+      ci = ci0;
+      rperm_h.clear();
+      vperm_h.clear();
+    } else {
+      std::vector<int32_t> rp2(m + 1, 0), ci2(std::max<int64_t>(nnz, 1)), vp2(std::max<int64_t>(nnz, 1));
+      for (int64_t p = 0; p < m; ++p) {
+        const int32_t r = rperm_b[p];
+        rp2[p + 1] = rp2[p] + (rp0[r + 1] - rp0[r]);
+        for (int32_t t = rp0[r], u = rp2[p]; t < rp0[r + 1]; ++t, ++u) {
+          ci2[u] = ci0[t];
+          vp2[u] = t;
+        }
+      }
+      rp.swap(rp2);
+      ci.swap(ci2);
+      rperm_h.swap(rperm_b);
+      vperm_h.swap(vp2);
+    }
+    chain_safe = cs;
+    chain_bw = cb;
+    lcols.assign(cand.begin(), cand.begin() + k);
+    std::sort(lcols.begin(), lcols.end());
+    break;
+  }
+  return msg;
+}
+
 inline size_t blk_off(const fpsq_band b, int64_t i, int64_t j) {  // block (i, j), i - (band_w - 1) <= j <= i
   return ((size_t)i * b->band_w + (size_t)(j - i + b->band_w - 1)) * kDB * kDB;
 }
@@ -346,6 +429,23 @@ void border_correct(fpsq_band b, double* y) {
                      b->bd_t, y, (int)b->mb, b->border);
 }
 
+// The correction of an M-solve on a handle with long columns, behind the sweeps (y as above): all rows hold B^-1 r; afterwards
+// they hold M^-1 r = y - Z w and the virtual rows behind row mpad hold w = U'(y - Z w)
+template <int NC>
+void cols_correct(fpsq_band b, double* y) {
+  hipLaunchKernelGGL(k_border_reduce<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_c, y, (int)b->m, 0, b->bd_part,
+                     b->bd_t);
+  hipLaunchKernelGGL(k_cols_update<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_z, b->bd_l, b->bd_part, b->bd_grid, y,
+                     (int)b->m, (int)b->mpad);
+}
+
+// the chunk sums of U'keep into the virtual rows of an operand the A' kernels read beside the solutions (keep: [mpad + vrows][NC])
+template <int NC>
+void cols_keep(fpsq_band b, double* keep) {
+  hipLaunchKernelGGL(k_border_reduce<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_c, keep, (int)b->m, 0,
+                     keep + (size_t)b->mpad * NC, b->bd_t);
+}
+
 void band_sweeps(fpsq_band b);
 
 // q (in b->r2, [mpad][2]) <- M^-1 r2 with the banded factor (and the border's correction, whichever form the sweeps take);
@@ -353,6 +453,7 @@ void band_sweeps(fpsq_band b);
 void band_solve(fpsq_band b) {
   band_sweeps(b);
   if (b->border) border_correct<2>(b, b->r2);
+  if (b->cols) cols_correct<2>(b, b->r2);
 }
 
 // the sweeps on the band rows: b->r2 <- B^-1 b->r2 (rows beyond the band's blocks are not touched)
@@ -428,12 +529,17 @@ struct BandSymbolic {
   int maxspan = 1, chain_safe = 0, chain_bw = 0;  // (maxspan: over the band rows)
   int64_t bwb = 0;  // half bandwidth in blocks (of the band rows)
   int border = 0;   // rows stored last and eliminated as a border
+  // long columns (ascending), the workgroups of their reductions, their entries column by column (stored row / entry), and
+  // the CSR of the other columns alone with its entries among the stored ones (k_band_form)
+  std::vector<int32_t> lcols, lc_ptr, lc_row, lc_ent, rp_b, ci_b, perm_b;
+  int vgrid = 0;
+  int64_t t_nnz = 0;
 };
 
 // Validate and order on the host (the role of ldl_analyze, src/solve_two_systems_struct.jl:344): the structure of
 // A A' + delta I is a band whose half width is the largest row distance of two entries of one column of A.  Reads the
 // caller's CSR (host or device memory); returns an error text, empty on success.
-std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int max_border,
+std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int max_border, int max_cols,
                           BandSymbolic& sy) {
   std::vector<int32_t>&rp = sy.rp, &ci = sy.ci;
   rp.resize(m + 1);
@@ -443,9 +549,17 @@ std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int
   ci.resize(std::max<int64_t>(nnz, 1));
   if (nnz > 0 && (!colind || hipMemcpy(ci.data(), colind, (size_t)nnz * 4, hipMemcpyDefault) != hipSuccess))
     return "fpsq_band_create: cannot read colind";
-  const std::string msg = band_order(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_border, sy.border);
+  const std::string msg =
+      max_cols > 0 ? band_order_cols(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_cols, sy.lcols)
+                   : band_order(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_border, sy.border);
   if (!msg.empty()) return msg;
   const int64_t mb = m - sy.border;
+  const int ncols = (int)sy.lcols.size();
+  const int64_t mpad = (m + kDB - 1) / kDB * kDB;
+  sy.vgrid = ncols ? (int)std::max<int64_t>(1, std::min<int64_t>((m + 255) / 256, kBorderGrid)) : 0;
+  std::vector<int8_t> lidx(ncols ? n : 0, -1);  // column -> its place among the long ones
+  for (int i = 0; i < ncols; ++i) lidx[sy.lcols[i]] = (int8_t)i;
+  auto is_long = [&](int32_t c) { return ncols && lidx[c] >= 0; };
   std::vector<int32_t> cfirst(n, INT32_MAX), clast(n, -1), seen(n, -1);
   std::vector<int32_t>& tcnt = sy.tptr;
   tcnt.assign(n + 1, 0);
@@ -455,10 +569,11 @@ std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int
     int lo = INT32_MAX, hi = -1;
     for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
       const int32_t c = ci[k];
-      lo = std::min(lo, c);
-      hi = std::max(hi, c);
       has_dup |= seen[c] == (int32_t)i;
       seen[c] = (int32_t)i;
+      if (is_long(c)) continue;  // (neither in a span nor in the band; its transposed entries are virtual, below)
+      lo = std::min(lo, c);
+      hi = std::max(hi, c);
       if (i < mb) {
         cfirst[c] = std::min<int32_t>(cfirst[c], (int32_t)i);
         clast[c] = std::max<int32_t>(clast[c], (int32_t)i);
@@ -472,16 +587,45 @@ std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int
   if (has_dup) return "fpsq_band_create: the CSR pattern has duplicate entries (sum them first)";
   for (int64_t c = 0; c < n; ++c)
     if (clast[c] >= 0) sy.bwb = std::max<int64_t>(sy.bwb, clast[c] / kDB - cfirst[c] / kDB);
+  for (int i = 0; i < ncols; ++i) tcnt[sy.lcols[i] + 1] = sy.vgrid;
   for (int64_t c = 0; c < n; ++c) tcnt[c + 1] += tcnt[c];
-  sy.trow.resize(std::max<int64_t>(nnz, 1));
-  sy.tperm.resize(std::max<int64_t>(nnz, 1));
+  sy.t_nnz = tcnt[n];
+  sy.trow.resize(std::max<int64_t>(sy.t_nnz, 1));
+  sy.tperm.resize(std::max<int64_t>(sy.t_nnz, 1));
   std::vector<int32_t> nxt(tcnt.begin(), tcnt.end() - 1);
-  for (int64_t i = 0; i < m; ++i)
+  std::vector<std::vector<int32_t>> lrow(ncols), lent(ncols);
+  if (ncols) sy.rp_b.assign(1, 0);
+  for (int64_t i = 0; i < m; ++i) {
     for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
+      if (is_long(ci[k])) {
+        lrow[lidx[ci[k]]].push_back((int32_t)i);
+        lent[lidx[ci[k]]].push_back(k);
+        continue;
+      }
       const int32_t t = nxt[ci[k]]++;
       sy.trow[t] = (int32_t)i;
       sy.tperm[t] = k;
+      if (ncols) {
+        sy.ci_b.push_back(ci[k]);
+        sy.perm_b.push_back(k);
+      }
     }
+    if (ncols) sy.rp_b.push_back((int32_t)sy.ci_b.size());
+  }
+  if (ncols) {
+    sy.lc_ptr.assign(1, 0);
+    for (int i = 0; i < ncols; ++i) {
+      // virtual row mpad + 16 g + i holds workgroup g's share of U[.][i]'q; the value slot behind the last entry holds 1
+      for (int g = 0; g < sy.vgrid; ++g) {
+        const int32_t t = nxt[sy.lcols[i]]++;
+        sy.trow[t] = (int32_t)(mpad + (int64_t)kBorderMax * g + i);
+        sy.tperm[t] = (int32_t)nnz;
+      }
+      sy.lc_row.insert(sy.lc_row.end(), lrow[i].begin(), lrow[i].end());
+      sy.lc_ent.insert(sy.lc_ent.end(), lent[i].begin(), lent[i].end());
+      sy.lc_ptr.push_back((int32_t)sy.lc_row.size());
+    }
+  }
   return std::string();
 }
 
@@ -525,10 +669,11 @@ int band_alloc(fpsq_band b) {
   hipEventCreateWithFlags(&b->evA, hipEventDisableTiming);
   hipEventCreateWithFlags(&b->evB, hipEventDisableTiming);
   const size_t n = (size_t)b->n, m = (size_t)b->m, nz = (size_t)std::max<int64_t>(b->nnz, 1);
+  const size_t tz = (size_t)std::max<int64_t>(b->t_nnz, 1);  // (= nz without long columns)
   int rc = core_setup(b, b->n);
-  rc |= dalloc(b, &b->rowptr, m + 1) | dalloc(b, &b->colind, nz) | dalloc(b, &b->vals, nz);
-  rc |= dalloc(b, &b->t_rowptr, n + 1) | dalloc(b, &b->t_colind, nz) | dalloc(b, &b->t_vals, nz);
-  rc |= dalloc(b, &b->t_perm, nz) | dalloc(b, &b->rowspan, m);
+  rc |= dalloc(b, &b->rowptr, m + 1) | dalloc(b, &b->colind, nz) | dalloc(b, &b->vals, nz + (b->cols ? 1 : 0));
+  rc |= dalloc(b, &b->t_rowptr, n + 1) | dalloc(b, &b->t_colind, tz) | dalloc(b, &b->t_vals, tz);
+  rc |= dalloc(b, &b->t_perm, tz) | dalloc(b, &b->rowspan, m);
   rc |= dalloc(b, &b->Mb, (size_t)b->nb * b->band_w * kDB * kDB);
   rc |= dalloc(b, &b->xn, n * 2) | dalloc(b, &b->atq, n * 2) | dalloc(b, &b->ym, (size_t)b->mpad * 2);
   if (b->reordered)
@@ -551,12 +696,76 @@ void band_upload(fpsq_band b, const BandSymbolic& sy) {
   hipMemcpy(b->rowptr, sy.rp.data(), (m + 1) * 4, hipMemcpyHostToDevice);
   hipMemcpy(b->t_rowptr, sy.tptr.data(), (n + 1) * 4, hipMemcpyHostToDevice);
   hipMemcpy(b->rowspan, sy.span.data(), m * sizeof(int2), hipMemcpyHostToDevice);
-  if (nnz > 0) {
-    hipMemcpy(b->colind, sy.ci.data(), nnz * 4, hipMemcpyHostToDevice);
-    hipMemcpy(b->t_colind, sy.trow.data(), nnz * 4, hipMemcpyHostToDevice);
-    hipMemcpy(b->t_perm, sy.tperm.data(), nnz * 4, hipMemcpyHostToDevice);
+  const size_t tnz = (size_t)b->t_nnz;
+  if (nnz > 0) hipMemcpy(b->colind, sy.ci.data(), nnz * 4, hipMemcpyHostToDevice);
+  if (tnz > 0) {
+    hipMemcpy(b->t_colind, sy.trow.data(), tnz * 4, hipMemcpyHostToDevice);
+    hipMemcpy(b->t_perm, sy.tperm.data(), tnz * 4, hipMemcpyHostToDevice);
+  }
+  if (b->cols) {  // the value the virtual entries of the transposed structure gather
+    const double one = 1.0;
+    hipMemcpy(b->vals + nnz, &one, 8, hipMemcpyHostToDevice);
   }
   hipDeviceSynchronize();
+}
+
+// The buffers of a handle with long columns: the block sweeps' own (Z = B^-1 U is one tile of them), U, Z, the factor of S, the
+// partial sums, the operand with virtual rows, the columns' entries, and for k_band_form the CSR of the other columns.
+// Non-zero (the handle is destroyed): failed.
+int cols_setup(fpsq_band b, const BandSymbolic& sy) {
+  if (b->cols == 0) return FPSQ_OK;
+  b->bd_grid = sy.vgrid;
+  hipEventCreate(&b->evS0);
+  hipEventCreate(&b->evS1);
+  const size_t tile = (size_t)b->mpad * kBlkCols, nl = std::max<size_t>(sy.lc_row.size(), 1);
+  int rc = chain16_setup(b) || dalloc(b, &b->bd_c, tile) || dalloc(b, &b->bd_z, tile) ||
+           dalloc(b, &b->bd_l, (size_t)kBorderMax * kBorderMax) || dalloc(b, &b->bd_part, (size_t)b->bd_grid * 256) ||
+           dalloc(b, &b->bd_t, 256 + 8) || dalloc(b, &b->bd_keep, (size_t)(b->mpad + b->vrows)) ||
+           dalloc(b, &b->lc_ptr, (size_t)b->cols + 1) || dalloc(b, &b->lc_row, nl) || dalloc(b, &b->lc_ent, nl);
+  if (!rc && b->form_gen == 1) {
+    b->fb_nnz = (int64_t)sy.perm_b.size();
+    const size_t fz = (size_t)std::max<int64_t>(b->fb_nnz, 1);
+    rc = dalloc(b, &b->fb_rowptr, (size_t)b->m + 1) || dalloc(b, &b->fb_colind, fz) || dalloc(b, &b->fb_perm, fz) ||
+         dalloc(b, &b->fb_vals, fz);
+  }
+  if (rc) {
+    g_band_create_error = b->err;
+    fpsq_band_destroy(b);
+    return FPSQ_ERR_HIP;
+  }
+  hipMemset(b->bd_keep, 0, (size_t)(b->mpad + b->vrows) * 8);
+  hipMemcpy(b->lc_ptr, sy.lc_ptr.data(), ((size_t)b->cols + 1) * 4, hipMemcpyHostToDevice);
+  if (!sy.lc_row.empty()) {
+    hipMemcpy(b->lc_row, sy.lc_row.data(), sy.lc_row.size() * 4, hipMemcpyHostToDevice);
+    hipMemcpy(b->lc_ent, sy.lc_ent.data(), sy.lc_ent.size() * 4, hipMemcpyHostToDevice);
+  }
+  if (b->form_gen == 1) {
+    hipMemcpy(b->fb_rowptr, sy.rp_b.data(), ((size_t)b->m + 1) * 4, hipMemcpyHostToDevice);
+    if (b->fb_nnz > 0) {
+      hipMemcpy(b->fb_colind, sy.ci_b.data(), (size_t)b->fb_nnz * 4, hipMemcpyHostToDevice);
+      hipMemcpy(b->fb_perm, sy.perm_b.data(), (size_t)b->fb_nnz * 4, hipMemcpyHostToDevice);
+    }
+  }
+  hipDeviceSynchronize();
+  return FPSQ_OK;
+}
+
+// The long columns' share of a factorisation, behind the band's Cholesky on b->stream: U scattered from the current values,
+// Z = B^-1 U by the 16-column sweeps, the partials of U'Z, S = I + U'Z and its Cholesky
+void cols_factor(fpsq_band b) {
+  hipStream_t s = b->stream;
+  const size_t tile = (size_t)b->mpad * kBlkCols * 8;
+  hipEventRecord(b->evS0, s);
+  hipMemsetAsync(b->bd_c, 0, tile, s);
+  hipLaunchKernelGGL(k_cols_scatter, dim3(b->cols, 64), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->vals, b->bd_c);
+  hipMemcpyAsync(b->r16, b->bd_c, tile, hipMemcpyDeviceToDevice, s);
+  chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
+  hipMemcpyAsync(b->bd_z, b->r16, tile, hipMemcpyDeviceToDevice, s);
+  hipLaunchKernelGGL(k_border_reduce<kBlkCols>, dim3(b->bd_grid), dim3(256), 0, s, b->bd_c, b->bd_z, (int)b->m, 0, b->bd_part,
+                     b->bd_t);
+  hipLaunchKernelGGL(k_cols_chol, dim3(1), dim3(256), 0, s, b->bd_part, b->bd_grid, b->cols, (int)b->m, b->piv_tol, b->piv_reg,
+                     b->bd_l, b->bd_t + 256, b->info_dev);
+  hipEventRecord(b->evS1, s);
 }
 
 // The buffers of a bordered handle: the block sweeps' own (Z = B^-1 C is one tile of them) with the tile A multiplies, C, Z,
@@ -599,6 +808,14 @@ void border_factor(fpsq_band b, double delta) {
                      b->piv_reg, b->bd_l, b->info_dev);
   hipEventRecord(b->evS1, s);
 }
+
+// the check of max_cols every entry that takes it makes before anything else: null = fine
+const char* bad_max_cols(int32_t max_border, int32_t max_cols) {
+  if (max_cols < 0 || max_cols > kBorderMax) return "max_cols must be 0 .. 16";
+  if (max_border > 0 && max_cols > 0)
+    return "max_border > 0 together with max_cols > 0: a handle takes one kind of border, rows or columns";
+  return nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -612,8 +829,17 @@ int fpsq_band_analyze(int64_t n, int64_t m, const int32_t* rowptr, const int32_t
 
 int fpsq_band_analyze_bordered(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border,
                                int32_t* row_perm, fpsq_band_info* info) {
+  return fpsq_band_analyze_bordered_cols(n, m, rowptr, colind, max_border, 0, row_perm, nullptr, info);
+}
+
+int fpsq_band_analyze_bordered_cols(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border,
+                                    int32_t max_cols, int32_t* row_perm, int32_t* long_cols, fpsq_band_info* info) {
   if (max_border < 0 || max_border > kBorderMax) {
     g_band_create_error = "fpsq_band_analyze: max_border must be 0 .. 16";
+    return FPSQ_ERR_ARG;
+  }
+  if (const char* what = bad_max_cols(max_border, max_cols)) {
+    g_band_create_error = std::string("fpsq_band_analyze: ") + what;
     return FPSQ_ERR_ARG;
   }
   if (n <= 0 || m <= 0 || !rowptr || n >= INT32_MAX || m >= INT32_MAX - 256 || rowptr[0] != 0) {
@@ -634,10 +860,25 @@ int fpsq_band_analyze_bordered(int64_t n, int64_t m, const int32_t* rowptr, cons
   std::vector<int32_t> ci(colind, colind + nnz), rperm_h, vperm_h;
   ci.resize(std::max<int64_t>(nnz, 1));
   int chain_safe = 0, chain_bw = 0, border = 0;
-  const std::string msg = band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, border);
+  std::vector<int32_t> lcols;
+  const std::string msg = max_cols > 0
+                              ? band_order_cols(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_cols, lcols)
+                              : band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, border);
   if (!msg.empty()) {
     g_band_create_error = msg;
     return FPSQ_ERR_ARG;
+  }
+  if (long_cols)
+    for (int i = 0; i < kBorderMax; ++i) long_cols[i] = i < (int)lcols.size() ? lcols[i] : -1;
+  if (!lcols.empty()) {  // the band is that of the other columns: drop the long ones from the structure that is measured
+    std::vector<char> out(n, 0);
+    for (int32_t c : lcols) out[c] = 1;
+    int32_t w = 0;
+    for (int64_t i = 0, k = 0; i < m; ++i) {
+      for (const int32_t e = rp[i + 1]; k < e; ++k)
+        if (!out[ci[k]]) ci[w++] = ci[k];
+      rp[i + 1] = w;
+    }
   }
   if (row_perm)
     for (int64_t p = 0; p < m; ++p) row_perm[p] = rperm_h.empty() ? (int32_t)p : rperm_h[p];
@@ -649,6 +890,8 @@ int fpsq_band_analyze_bordered(int64_t n, int64_t m, const int32_t* rowptr, cons
     info->n = n;
     info->m = m;
     info->nnz = nnz;
+    info->border_cols = (int64_t)lcols.size();
+    info->border_pivot_ratio = 1.0;
     info->nblocks = nb;
     info->bandwidth_blocks = bwb;
     info->factor_bytes = nb * (bwb + 1) * (int64_t)kDB * kDB * 8;
@@ -681,8 +924,17 @@ int fpsq_band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr
 
 int fpsq_band_create_bordered(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind,
                               int32_t max_border, int32_t device) {
+  return fpsq_band_create_bordered_cols(out, n, m, rowptr, colind, max_border, 0, device);
+}
+
+int fpsq_band_create_bordered_cols(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind,
+                                   int32_t max_border, int32_t max_cols, int32_t device) {
   if (max_border < 0 || max_border > kBorderMax) {
     g_band_create_error = "fpsq_band_create: max_border must be 0 .. 16";
+    return FPSQ_ERR_ARG;
+  }
+  if (const char* what = bad_max_cols(max_border, max_cols)) {
+    g_band_create_error = std::string("fpsq_band_create: ") + what;
     return FPSQ_ERR_ARG;
   }
   if (!out || n <= 0 || m <= 0 || !rowptr || n >= INT32_MAX || m >= INT32_MAX - 256) {
@@ -701,7 +953,7 @@ int fpsq_band_create_bordered(fpsq_band* out, int64_t n, int64_t m, const int32_
     return FPSQ_ERR_HIP;
   }
   BandSymbolic sy;
-  const std::string msg = band_symbolic(n, m, rowptr, colind, max_border, sy);
+  const std::string msg = band_symbolic(n, m, rowptr, colind, max_border, max_cols, sy);
   if (!msg.empty()) {
     g_band_create_error = msg;
     return FPSQ_ERR_ARG;
@@ -714,6 +966,9 @@ int fpsq_band_create_bordered(fpsq_band* out, int64_t n, int64_t m, const int32_
   b->device = device;
   b->border = sy.border;
   b->mb = m - sy.border;
+  b->cols = (int)sy.lcols.size();
+  b->t_nnz = sy.t_nnz;
+  b->vrows = (int64_t)kBorderMax * sy.vgrid;
   b->mpad = (m + kDB - 1) / kDB * kDB;
   b->nb = (b->mb + kDB - 1) / kDB;  // (the blocks of the band rows; = mpad / 128 without a border)
   b->band_w = (int)std::min<int64_t>(sy.bwb, b->nb - 1) + 1;
@@ -726,6 +981,10 @@ int fpsq_band_create_bordered(fpsq_band* out, int64_t n, int64_t m, const int32_
   if (int rc = band_alloc(b)) return rc;
   band_upload(b, sy);
   if (int rc = border_setup(b)) {
+    *out = nullptr;
+    return rc;
+  }
+  if (int rc = cols_setup(b, sy)) {
     *out = nullptr;
     return rc;
   }
@@ -746,6 +1005,8 @@ int fpsq_band_create_bordered(fpsq_band* out, int64_t n, int64_t m, const int32_
   b->info.chains = b->chain_safe > 0 ? 2 : 1;
   b->info.factor_bytes = (int64_t)band_factor_bytes(b);
   b->info.border_rows = b->border;
+  b->info.border_cols = b->cols;
+  b->info.border_pivot_ratio = 1.0;
   *out = b;
   return FPSQ_OK;
 }
@@ -757,8 +1018,18 @@ int fpsq_band_create_coo(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, cons
 
 int fpsq_band_create_coo_bordered(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
                                   int32_t index_base, int32_t max_border, int32_t device) {
+  return fpsq_band_create_coo_bordered_cols(out, n, m, nnz, rows, cols, index_base, max_border, 0, device);
+}
+
+int fpsq_band_create_coo_bordered_cols(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows,
+                                       const int64_t* cols, int32_t index_base, int32_t max_border, int32_t max_cols,
+                                       int32_t device) {
   if (max_border < 0 || max_border > kBorderMax) {
     g_band_create_error = "fpsq_band_create_coo: max_border must be 0 .. 16";
+    return FPSQ_ERR_ARG;
+  }
+  if (const char* what = bad_max_cols(max_border, max_cols)) {
+    g_band_create_error = std::string("fpsq_band_create_coo: ") + what;
     return FPSQ_ERR_ARG;
   }
   if (!out || n <= 0 || m <= 0 || nnz < 0 || nnz >= INT32_MAX || (nnz > 0 && (!rows || !cols))) {
@@ -785,7 +1056,7 @@ int fpsq_band_create_coo_bordered(fpsq_band* out, int64_t n, int64_t m, int64_t 
   std::vector<int32_t> rp(m + 1, 0);
   for (int64_t i = 0; i < ns; ++i) rp[srow[i] + 1]++;
   for (int64_t i = 0; i < m; ++i) rp[i + 1] += rp[i];
-  if (int rc = fpsq_band_create_bordered(out, n, m, rp.data(), scol.data(), max_border, device)) return rc;
+  if (int rc = fpsq_band_create_bordered_cols(out, n, m, rp.data(), scol.data(), max_border, max_cols, device)) return rc;
   fpsq_band b = *out;
   const bool dup = ns != nnz;
   if (dalloc(b, &b->coo_perm, (size_t)std::max<int64_t>(nnz, 1)) || dalloc(b, &b->coo_in, (size_t)std::max<int64_t>(nnz, 1)) ||
@@ -832,16 +1103,21 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
     } else {
       CHK(b, hipMemcpyAsync(b->vals, vals, (size_t)b->nnz * 8, hipMemcpyDefault, s));
     }
-    hipLaunchKernelGGL(k_gather_d, dim3((unsigned)std::min<int64_t>((b->nnz + 255) / 256, 4096)), dim3(256), 0, s, b->vals,
-                       b->t_perm, b->t_vals, b->nnz);
+    hipLaunchKernelGGL(k_gather_d, dim3((unsigned)std::min<int64_t>((b->t_nnz + 255) / 256, 4096)), dim3(256), 0, s, b->vals,
+                       b->t_perm, b->t_vals, b->t_nnz);
+    if (b->fb_nnz > 0)  // (long columns and k_band_form: the values of the other columns alone)
+      hipLaunchKernelGGL(k_gather_d, dim3((unsigned)std::min<int64_t>((b->fb_nnz + 255) / 256, 4096)), dim3(256), 0, s, b->vals,
+                         b->fb_perm, b->fb_vals, b->fb_nnz);
   }
   CHK(b, hipMemsetAsync(b->info_dev, 0, 8, s));
   CHK(b, hipMemsetAsync(b->Mb, 0, (size_t)nb * W * kDB * kDB * 8, s));
   hipEventRecord(b->e0, s);
   // numeric phase 1: M = A A' + delta I into the band (jac_coord! + sparse(...) of src/solve_linear_system.jl:223-233)
+  // (with long columns both kernels form B: k_band_form on the CSR of the other columns, k_band_form_t by its j <= i guard)
   if (b->form_gen == 1)
-    hipLaunchKernelGGL(k_band_form, dim3(nb), dim3(256), (size_t)b->span * 16, s, b->rowptr, b->colind, b->vals, b->rowspan,
-                       (int)b->mb, nb * kDB, W, delta, b->Mb, b->span);
+    hipLaunchKernelGGL(k_band_form, dim3(nb), dim3(256), (size_t)b->span * 16, s, b->cols ? b->fb_rowptr : b->rowptr,
+                       b->cols ? b->fb_colind : b->colind, b->cols ? b->fb_vals : b->vals, b->rowspan, (int)b->mb, nb * kDB, W,
+                       delta, b->Mb, b->span);
   else
     hipLaunchKernelGGL(k_band_form_t, dim3(nb), dim3(256), (size_t)b->form_R * W * kDB * 8, s, b->rowptr, b->colind, b->vals,
                        b->t_rowptr, b->t_colind, b->t_vals, (int)b->mb, nb * kDB, W, delta, b->Mb, b->form_R);
@@ -878,9 +1154,10 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
   }
   for (int k = k0; k < nb; ++k) step(s, k, 1, std::min(bw, nb - 1 - k));
   if (b->border) border_factor(b, delta);
+  if (b->cols) cols_factor(b);
   int32_t pivot = 0;
   const int rc = factor_end(b, &b->info.last_form_ms, &b->info.last_chol_ms, &b->info.regularized_pivots, &pivot);
-  if (b->border) {
+  if (b->border || b->cols) {
     // the sweeps that formed Z may have raised the error word: it is looked at and cleared HERE, whatever the code above, so
     // that it never surfaces as the time-out of a later, unrelated solve
     const bool expired = *b->chain_err != 0;
@@ -890,6 +1167,7 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
       hipEventElapsedTime(&ms, b->evS0, b->evS1);
       b->info.last_border_ms = ms;
       b->info.last_chol_ms -= ms;  // (the band's Cholesky alone, as on a handle without a border)
+      if (b->cols) CHK(b, hipMemcpy(&b->info.border_pivot_ratio, b->bd_t + 256, 8, hipMemcpyDeviceToHost));
       if (expired) {
         b->factored = false;
         b->err = "band_factorize: Z = B^-1 C did not arrive (bounded wait of the block sweep expired)";
@@ -956,7 +1234,7 @@ void bq_launches(fpsq_band b, fpsq_band_qp qp, bool hp, const double* x, const d
                  double eta, double* out, double* gs, double* ys) {
   hipStream_t s = b->stream;
   const int n = (int)b->n, m = (int)b->m, mpad = (int)b->mpad;
-  double* keep = b->o_q2;
+  double* keep = b->cols ? b->bd_keep : b->o_q2;  // (long columns: the operand has virtual rows)
   if (qp->sparse_q) {
     WITH_LANE_GROUP(qp->lgR, WITH_BOOL(hp, HP, hipLaunchKernelGGL((k_bq_pack_sq<LG, HP>), dim3(qp->gridR), dim3(256), 0, s,
                                                                   qp->r_rowptr, qp->r_colind, qp->r_vals, x, qp->q, qp->d,
@@ -967,6 +1245,7 @@ void bq_launches(fpsq_band b, fpsq_band_qp qp, bool hp, const double* x, const d
   WITH_LANE_GROUP(qp->lgA, WITH_BOOL(hp, HP, WITH_BOOL(qp->gather_g, GM, hipLaunchKernelGGL(
       (k_bq_prologue<LG, HP, GM>), dim3(qp->gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, b->xn, x, qp->q, qp->d,
       qp->bp, b->r2, keep, qp->partP, m, mpad, n))))
+  if (b->cols) cols_keep<1>(b, keep);
   band_solve(b);
   if (!qp->sparse_q) {
     WITH_LANE_GROUP(qp->lgT, WITH_BOOL(hp, HP, hipLaunchKernelGGL(
@@ -1150,7 +1429,17 @@ int fpsq_band_jac_mul(fpsq_band b, int32_t trans, double alpha, const double* x,
     if (int rc = stage_in(b, ay)) return rc;
   double *dx = ax.tile(), *dy = ay.tile();
   const int lg = lane_group(b->nnz, (int64_t)ny);
-  if (trans) {
+  if (trans && b->cols) {
+    // x into the stored row order, the long columns' rows of A'x by the reduction into its virtual rows, then the product
+    if (b->reordered)
+      hipLaunchKernelGGL(k_gather_d, grid256(b->m), dim3(256), 0, s, dx, b->rperm, b->bd_keep, b->m);
+    else
+      CHK(b, hipMemcpyAsync(b->bd_keep, dx, (size_t)b->m * 8, hipMemcpyDeviceToDevice, s));
+    cols_keep<1>(b, b->bd_keep);
+    WITH_LANE_GROUP(lg, hipLaunchKernelGGL(k_bq_jacmul<LG>, dim3(bq_grid(b->n, lg)), dim3(256), 0, s, b->t_rowptr, b->t_colind,
+                                           b->t_vals, (const int32_t*)nullptr, (const int32_t*)nullptr, alpha, b->bd_keep, beta,
+                                           dy, (int)b->n))
+  } else if (trans) {
     WITH_LANE_GROUP(lg, hipLaunchKernelGGL(k_bq_jacmul<LG>, dim3(bq_grid(b->n, lg)), dim3(256), 0, s, b->t_rowptr, b->t_colind,
                                            b->t_vals, b->row_perm(), (const int32_t*)nullptr, alpha, dx, beta, dy, (int)b->n))
   } else {
@@ -1182,7 +1471,7 @@ int blk_arg(fpsq_band b, const double* p, size_t len, int slot, StagedArg* a) {
 int blk_setup(fpsq_band b, bool keep, bool tv) {
   if (int rc = chain16_setup(b)) return rc;
   if (!b->blk_xg && dalloc(b, &b->blk_xg, (size_t)b->n * kBlkCols)) return FPSQ_ERR_HIP;
-  if (keep && !b->blk_keep && dalloc(b, &b->blk_keep, (size_t)b->mpad * kBlkVec)) return FPSQ_ERR_HIP;
+  if (keep && !b->blk_keep && dalloc(b, &b->blk_keep, (size_t)(b->mpad + b->vrows) * kBlkVec)) return FPSQ_ERR_HIP;
   if (tv && !b->blk_tv && dalloc(b, &b->blk_tv, (size_t)b->n * kBlkVec)) return FPSQ_ERR_HIP;
   return FPSQ_OK;
 }
@@ -1191,12 +1480,14 @@ int blk_setup(fpsq_band b, bool keep, bool tv) {
 void blk_sweeps(fpsq_band b) {
   chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
   if (b->border) border_correct<kBlkCols>(b, b->r16);
+  if (b->cols) cols_correct<kBlkCols>(b, b->r16);
 }
 
 // A xg into the sweeps' layout, then the two sweeps
 void blk_solve_tile(fpsq_band b, int lgA, double* keep) {
   WITH_LANE_GROUP(lgA, hipLaunchKernelGGL(k_bqb_prologue<LG>, dim3(bq_grid(b->mpad, lgA)), dim3(256), 0, b->stream, b->rowptr,
                                           b->colind, b->vals, b->blk_xg, b->r16, keep, (int)b->m, (int)b->mpad))
+  if (b->cols && keep) cols_keep<kBlkVec>(b, keep);
   blk_sweeps(b);
 }
 
@@ -1360,6 +1651,7 @@ int fpsq_band_qp_objgrad_block(fpsq_band b, fpsq_band_qp qp, int32_t k, const do
     WITH_LANE_GROUP(qp->lgA, WITH_BOOL(!qp->sparse_q, FD, hipLaunchKernelGGL(
         (k_bqb_og_prologue<LG, FD>), dim3(qp->gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, b->blk_xg, dx, dd, qp->d,
         qp->q, db, qp->bp, b->row_perm(), b->r16, b->blk_keep, b->og_partP, (int)m, (int)b->mpad, (int)n, kt)))
+    if (b->cols) cols_keep<kBlkVec>(b, b->blk_keep);
     blk_sweeps(b);
     WITH_LANE_GROUP(qp->lgT, WITH_BOOL(qp->sparse_q, SQ, hipLaunchKernelGGL(
         (k_bqb_og_epilogue<LG, SQ>), dim3(qp->gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, b->r16, b->blk_keep,

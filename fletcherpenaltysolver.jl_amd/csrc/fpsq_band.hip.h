@@ -1200,4 +1200,126 @@ __global__ __launch_bounds__(256) void k_border_chol(const double* __restrict__ 
   }
 }
 
+// ---- long columns (fpsq_band_create_bordered_cols): the s <= kBorderMax columns of A taken out of the band, A = [A_b | U],
+//   M = B + U U',  B = A_b A_b' + delta I (the band the sweeps factor),  M^-1 r = y - Z w,  y = B^-1 r,  Z = B^-1 U,
+//   S = I + U'Z,  w = S^-1 (U'y).
+// A factorisation keeps U and Z as [.][16] arrays in the stored row order (columns >= s zero) and the Cholesky factor of S; an
+// M-solve is the sweeps, then k_border_reduce with U in the place of C and no border rows (the partials of U'y), then
+// k_cols_update.  VIRTUAL ROWS: the transposed structure the A' kernels walk holds, for long column i, one entry of value 1
+// per workgroup g of the reduction, pointing at row mpad + 16 g + i of the vector -- slots behind the padded rows that no
+// sweep touches.  For an operand that is not a solution (keep, the x of fpsq_band_jac_mul(trans = 1)) k_border_reduce writes
+// its partials straight into those slots (their layout IS part[g][i][c]); for the solutions k_cols_update leaves w in the
+// slots of g = 0 and zero in the others, since U'(y - Z w) = w.  The formation by columns skips a long column by its j <= i
+// guard (a virtual row lies beyond every row).  Sums in a fixed order, column c reads column c only, no atomics, no waits.
+
+// U[lc_row[t]][i] = vals[lc_ent[t]] over the entries t of long column i (stored row, stored entry); U is zeroed first
+__global__ __launch_bounds__(256) void k_cols_scatter(const int32_t* __restrict__ lc_ptr, const int32_t* __restrict__ lc_row,
+                                                      const int32_t* __restrict__ lc_ent, const double* __restrict__ vals,
+                                                      double* __restrict__ U) {
+  const int i = blockIdx.x, e = lc_ptr[i + 1];
+  for (int t = lc_ptr[i] + (int)blockIdx.y * 256 + (int)threadIdx.x; t < e; t += (int)gridDim.y * 256)
+    U[(size_t)lc_row[t] * kBorderMax + i] = vals[lc_ent[t]];
+}
+
+// every workgroup: g = the sum of the partials of U'y (index order), w = L'^-1 L^-1 g (one thread per column), then its own
+// slice of the rows, y[p][c] -= sum_i Z[p][i] w[i][c], and its own virtual rows: w for workgroup 0, zero for the others.
+// The grid is the grid of the reduction.  Ls: the factor of S, [16][16] row-major, lower, identity beyond s.
+template <int NC>
+__global__ __launch_bounds__(256) void k_cols_update(const double* __restrict__ Zm, const double* __restrict__ Ls,
+                                                     const double* __restrict__ part, int nparts, double* y, int m, int mpad) {
+  constexpr int NO = kBorderMax * NC;
+  __shared__ double L[kBorderMax * kBorderMax];
+  __shared__ double g[NO];
+  L[threadIdx.x] = Ls[threadIdx.x];
+  if (threadIdx.x < NO) {
+    double a = 0.0;
+    for (int q = 0; q < nparts; ++q) a += part[(size_t)q * NO + threadIdx.x];
+    g[threadIdx.x] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x < NC) {
+    const int c = threadIdx.x;
+    double w[kBorderMax];
+#pragma unroll
+    for (int i = 0; i < kBorderMax; ++i) {
+      double v = g[i * NC + c];
+#pragma unroll
+      for (int k = 0; k < i; ++k) v -= L[i * kBorderMax + k] * w[k];
+      w[i] = v / L[i * kBorderMax + i];
+    }
+#pragma unroll
+    for (int i = kBorderMax - 1; i >= 0; --i) {
+      double v = w[i];
+#pragma unroll
+      for (int k = i + 1; k < kBorderMax; ++k) v -= L[k * kBorderMax + i] * w[k];
+      w[i] = v / L[i * kBorderMax + i];
+    }
+#pragma unroll
+    for (int i = 0; i < kBorderMax; ++i) g[i * NC + c] = w[i];
+  }
+  __syncthreads();
+  const int chunk = (m + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int lo = min(m, (int)blockIdx.x * chunk), hi = min(m, lo + chunk);
+  for (int64_t idx = (int64_t)lo * NC + threadIdx.x; idx < (int64_t)hi * NC; idx += 256) {
+    const int64_t p = idx / NC;
+    const int c = (int)(idx % NC);
+    const double* z = Zm + (size_t)p * kBorderMax;
+    double a = 0.0;
+#pragma unroll
+    for (int i = 0; i < kBorderMax; ++i) a += z[i] * g[i * NC + c];
+    y[idx] -= a;
+  }
+  if (threadIdx.x < NO)  // (virtual row mpad + 16 blk + i, column c: blk * NO + i * NC + c behind row mpad)
+    y[(size_t)mpad * NC + (size_t)blockIdx.x * NO + threadIdx.x] = blockIdx.x == 0 ? g[threadIdx.x] : 0.0;
+}
+
+// One workgroup: S = I + U'Z from the partials of U'Z (k_border_reduce<16> on Z, summed in index order; the lower triangle
+// is used), then its Cholesky factor into Ls ([16][16], identity beyond s) and ratio[0] = (largest / smallest pivot of the
+// factor)^2.  Pivots by the rule of k_border_chol; a failing one is reported in info[0] as stored row m, 1-based, and only into
+// an empty word: S >= I whenever B is positive definite, so B's failing pivot, at a lower stored position, is there already.
+__global__ __launch_bounds__(256) void k_cols_chol(const double* __restrict__ part, int nparts, int s, int m, double tol,
+                                                   double reg, double* __restrict__ Ls, double* __restrict__ ratio, int* info) {
+  __shared__ double S[kBorderMax][kBorderMax + 1];
+  const int i = threadIdx.x / kBorderMax, j = threadIdx.x % kBorderMax;
+  {
+    double a = 0.0;
+    for (int q = 0; q < nparts; ++q) a += part[(size_t)q * 256 + threadIdx.x];
+    S[i][j] = (i == j ? 1.0 : 0.0) + (i < s && j < s ? a : 0.0);
+  }
+  __syncthreads();
+  const bool dyn = reg > 0.0;
+  const double thr = dyn ? tol : 0.0, sub = dyn ? reg : 1.0;
+  int nbad = 0;
+  for (int k = 0; k < s; ++k) {
+    if (threadIdx.x == 0) {
+      double d = S[k][k];
+      if (!(d > thr)) {
+        ++nbad;
+        d = sub;
+      }
+      S[k][k] = sqrt(d);
+    }
+    __syncthreads();
+    if (j == k && i > k) S[i][k] /= S[k][k];
+    __syncthreads();
+    if (j > k && i >= j) S[i][j] -= S[i][k] * S[j][k];
+    __syncthreads();
+  }
+  Ls[threadIdx.x] = j <= i ? S[i][j] : 0.0;
+  if (threadIdx.x == 0) {
+    double lo = S[0][0], hi = S[0][0];
+    for (int k = 1; k < s; ++k) {
+      lo = fmin(lo, S[k][k]);
+      hi = fmax(hi, S[k][k]);
+    }
+    ratio[0] = (hi / lo) * (hi / lo);
+    if (nbad) {
+      if (dyn)
+        atomicAdd(info + 1, nbad);
+      else
+        atomicCAS(info, 0, m);
+    }
+  }
+}
+
 }  // namespace fpsq

@@ -993,6 +993,7 @@ using namespace fpsq;
 struct DirectCore {
   const char* name = "";  // "dense" / "band": prefix of the state errors
   int64_t n = 0, m = 0, mpad = 0, nb = 0;
+  int64_t vrows = 0;  // slots behind row mpad of r2 / r16 that no sweep touches (fpsq_band: the long columns' virtual rows)
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
@@ -1100,7 +1101,7 @@ inline int core_setup(DirectCore* c, int64_t nlen) {
     hipMemset(c->invs, 0, inv_len * 8);
     hipMemset(c->invsT, 0, inv_len * 8);
   }
-  rc |= dalloc(c, &c->r2, (size_t)c->mpad * 2) | dalloc(c, &c->y2, (size_t)c->mpad * 2);
+  rc |= dalloc(c, &c->r2, (size_t)(c->mpad + c->vrows) * 2) | dalloc(c, &c->y2, (size_t)c->mpad * 2);
   rc |= dalloc(c, &c->in_a, (size_t)nlen) | dalloc(c, &c->in_b, (size_t)std::max(nlen, c->mpad));
   rc |= dalloc(c, &c->o_p1, (size_t)nlen) | dalloc(c, &c->o_p2, (size_t)nlen);
   rc |= dalloc(c, &c->o_q1, (size_t)c->mpad) | dalloc(c, &c->o_q2, (size_t)c->mpad) | dalloc(c, &c->info_dev, 4);
@@ -1211,7 +1212,7 @@ inline int chain16_setup(DirectCore* c) {
   if (c->blk_pub) return FPSQ_OK;
   const size_t pub_len = (size_t)c->nb * kBlkPub + 8;
   unsigned long long* pub = nullptr;
-  if (dalloc(c, &c->r16, (size_t)c->mpad * kBlkCols) || dalloc(c, &c->y16, (size_t)c->mpad * kBlkCols) ||
+  if (dalloc(c, &c->r16, (size_t)(c->mpad + c->vrows) * kBlkCols) || dalloc(c, &c->y16, (size_t)c->mpad * kBlkCols) ||
       dalloc(c, &pub, pub_len))
     return FPSQ_ERR_HIP;
   CHK(c, hipMemsetAsync(pub, 0, pub_len * 8, c->stream));

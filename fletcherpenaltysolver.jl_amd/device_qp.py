@@ -199,9 +199,11 @@ class DeviceBandEqQP:
     `set_delta` or `set_jacobian_values`; `info()["factorizations"]` counts how many this object has run.
     ldlt_tol / ldlt_r2: the dynamic regularisation of `LDLtSolver`, defaults as in qdsolver._DirectQDSolver (sqrt(eps),
     -sqrt(eps); "drop" drops a vanishing pivot).  Has the surface `fps_solve_device` uses on DeviceEqQP.
-    `border` (class attribute, 0 .. 16; DeviceBorderedBandEqQP sets it per object): the max_border the handle is created with."""
+    `border`, `cols` (class attributes, 0 .. 16; DeviceBorderedBandEqQP sets them per object): the max_border / max_cols the
+    handle is created with."""
 
     border = 0
+    cols = 0
 
     def __init__(self, qp, sigma=1e3, rho=1.0, delta=0.0, eta=0.0, device=0, ldlt_tol=None, ldlt_r2=None):
         from .qdsolver import _ldlt_r2
@@ -213,8 +215,8 @@ class DeviceBandEqQP:
         rp = np.ascontiguousarray(qp.rowptr, dtype=np.int32)
         ci = np.ascontiguousarray(qp.colind, dtype=np.int32)
         h = C.c_void_p()
-        if self._lib.fpsq_band_create_bordered(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, int(self.border),
-                                               self.device) != 0:
+        if self._lib.fpsq_band_create_bordered_cols(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, int(self.border),
+                                                    int(self.cols), self.device) != 0:
             raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
         self._h = h
         try:
@@ -396,11 +398,16 @@ class DeviceBorderedBandEqQP(DeviceBandEqQP):
     """DeviceBandEqQP on a BORDERED band: at most `border` (0 .. 16) long constraint rows -- rows that couple with every other
     row of M = A A' + delta I, such as a mean-value, volume or mass-conservation constraint or the wrap-around rows of a
     periodic boundary -- are eliminated last instead of widening the band (include/fpsq.h "BORDERED BAND").  Every method
-    is the base class's; `info()["border_rows"]` says how many rows were taken (0: the handle is DeviceBandEqQP's).  The
-    other keywords are DeviceBandEqQP's (whose parameter list stays as it is)."""
+    is the base class's; `info()["border_rows"]` says how many rows were taken (0: the handle is DeviceBandEqQP's).
+    `cols` (0 .. 16) is the transposed case: at most that many long COLUMNS -- a global parameter, a free final time, a
+    scalar control -- are taken out of the band and every M-solve is corrected by a low-rank term (include/fpsq.h "LONG
+    COLUMNS"); `info()["border_cols"]` says how many were taken and `info()["border_pivot_ratio"]` what the correction costs
+    in digits.  A handle takes ONE kind: pass `border=0` with `cols`.  The other keywords are DeviceBandEqQP's (whose parameter
+    list stays as it is)."""
 
-    def __init__(self, qp, border=16, **kwargs):
+    def __init__(self, qp, border=16, cols=0, **kwargs):
         self.border = int(border)
+        self.cols = int(cols)
         super().__init__(qp, **kwargs)
 
 

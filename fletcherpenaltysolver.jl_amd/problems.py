@@ -161,6 +161,44 @@ def with_border_rows(qp: EqQP, s: int, kind: str = "mean", seed: int = 0) -> EqQ
                                vals=np.concatenate([qp.vals, vals]), b=np.concatenate([qp.b, b_new]))
 
 
+def with_long_columns(qp: EqQP, s: int, kind: str = "param", seed: int = 0) -> EqQP:
+    """A copy of `qp` with `s` LONG columns appended (variables n .. n + s - 1): variables that appear in constraints all over
+    the row range, the case of include/fpsq.h "LONG COLUMNS".
+      kind = "param":  column j touches every row -- a global parameter, a free final time;
+      kind = "stride": column j touches the rows r with r % 4 == j % 4 -- a control shared by every fourth constraint.
+    Values (0.5 + u(seed, j * m + r, 41)) / sqrt(rows the column touches).  qdiag, d, xhat and x are extended by the streams
+    `_finish` uses, at index n + j, and b = A xhat is recomputed, so xhat stays feasible.  The QP must have a diagonal Hessian
+    (apply `with_sparse_hessian` afterwards for a sparse one)."""
+    import scipy.sparse as sp
+
+    s = int(s)
+    assert s >= 1 and qp.hess_vals is None
+    n, m = qp.n, qp.m
+    rows, cols, vals = [], [], []
+    for j in range(s):
+        if kind == "param":
+            r = np.arange(m, dtype=np.int64)
+        elif kind == "stride":
+            r = np.arange(j % 4, m, 4, dtype=np.int64)
+        else:
+            raise ValueError(f"kind must be 'param' or 'stride', not {kind!r}")
+        rows.append(r)
+        cols.append(np.full(r.size, n + j, dtype=np.int64))
+        vals.append((0.5 + uniform01(seed, j * m + r, 41)) / np.sqrt(r.size))
+    rows0 = np.repeat(np.arange(m, dtype=np.int64), np.diff(qp.rowptr))
+    A = sp.csr_matrix((np.concatenate([qp.vals] + vals), (np.concatenate([rows0] + rows),
+                                                          np.concatenate([qp.colind.astype(np.int64)] + cols))),
+                      shape=(m, n + s))   # (disjoint patterns: nothing is summed, the appended columns end each row)
+    A.sort_indices()
+    idx = n + np.arange(s)
+    xhat = np.concatenate([qp.xhat, 2.0 * uniform01(seed, idx, 3) - 1.0])
+    return dataclasses.replace(
+        qp, name=f"{qp.name}+{s}{kind}cols", n=n + s, rowptr=A.indptr.astype(np.int32), colind=A.indices.astype(np.int32),
+        vals=A.data.astype(np.float64), qdiag=np.concatenate([qp.qdiag, 1.0 + 9.0 * uniform01(seed, idx, 1)]),
+        d=np.concatenate([qp.d, 2.0 * uniform01(seed, idx, 2) - 1.0]), xhat=xhat, b=A @ xhat,
+        x=np.concatenate([qp.x, xhat[n:] + 0.1 * (2.0 * uniform01(seed, idx, 4) - 1.0)]))
+
+
 def _stratified_rows(m, n, per_row, start, width, seed, diag_col=None, diag_boost=0.0):
     """Each of the m rows gets `per_row` sorted, distinct columns: one per stratum of
     [start[i], start[i] + width).  If diag_col is given, the stratum containing diag_col[i] is

@@ -325,18 +325,20 @@ class HIPBandedDirectQDSolver(_DirectQDSolver):
     (solve_linear_system.jl:223-234), `solve_two_least_squares` re-uses the factor (:194-195); ldlt_tol / ldlt_r2 as in
     HIPDirectQDSolver.  border (0 .. 16): at most that many long constraint rows -- rows that couple with every other row
     of M, such as a mean-value constraint -- are eliminated last as a border instead of widening the band
-    (include/fpsq.h "BORDERED BAND"); `info()["border_rows"]` says how many were taken."""
+    (include/fpsq.h "BORDERED BAND"); `info()["border_rows"]` says how many were taken.  cols (0 .. 16): the same for long
+    COLUMNS, such as a global parameter (include/fpsq.h "LONG COLUMNS"; `info()["border_cols"]`); one kind per handle."""
 
     _prefix, _Info = "band", _lib.BandInfo
 
-    def __init__(self, nlp, _zero=0.0, *, border=0, **kwargs):
+    def __init__(self, nlp, _zero=0.0, *, border=0, cols=0, **kwargs):
         self.border = int(border)
+        self.cols = int(cols)
         super().__init__(nlp, _zero, **kwargs)
 
     def _create(self, rows, cols, device):
         b = C.c_void_p()
-        rc = self._lib.fpsq_band_create_coo_bordered(C.byref(b), self.nvar, self.ncon, rows.size, rows.ctypes.data,
-                                                     cols.ctypes.data, 1, self.border, device)
+        rc = self._lib.fpsq_band_create_coo_bordered_cols(C.byref(b), self.nvar, self.ncon, rows.size, rows.ctypes.data,
+                                                          cols.ctypes.data, 1, self.border, self.cols, device)
         if rc != 0:
             raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
         self._h = b
@@ -354,23 +356,24 @@ AUTO_MAX_BAND_BLOCKS = 4    # half bandwidth of M = A A' + delta I (in 128-row b
 AUTO_MAX_BLOCKS = 512       # ... and length of the elimination chain (128-row blocks of M) up to which it does
 
 
-def band_analysis(nlp, explicit_linear_constraints=False, border=0):
-    """The symbolic phase alone (fpsq_band_analyze_bordered: host only, no device): blocks / half bandwidth / factor bytes /
-    reordered / chains / border rows of the block-banded structure `HIPBandedDirectQDSolver(..., border=border)` would set up
-    for this model's Jacobian pattern."""
+def band_analysis(nlp, explicit_linear_constraints=False, border=0, cols=0):
+    """The symbolic phase alone (fpsq_band_analyze_bordered_cols: host only, no device): blocks / half bandwidth / factor
+    bytes / reordered / chains / border rows / long columns of the block-banded structure
+    `HIPBandedDirectQDSolver(..., border=border, cols=cols)` would set up for this model's Jacobian pattern."""
     import scipy.sparse as sp
 
     if explicit_linear_constraints:
         from .nlpmodels import NonlinearConstraintsView
         nlp = NonlinearConstraintsView(nlp)
     n, m = int(nlp.meta.nvar), int(nlp.meta.ncon)
-    rows, cols = nlp.jac_structure()
-    pat = sp.csr_matrix((np.ones(len(rows)), (np.asarray(rows) - 1, np.asarray(cols) - 1)), shape=(m, n))
+    jrows, jcols = nlp.jac_structure()
+    pat = sp.csr_matrix((np.ones(len(jrows)), (np.asarray(jrows) - 1, np.asarray(jcols) - 1)), shape=(m, n))
     pat.sum_duplicates()
     pat.sort_indices()
     rp, ci = pat.indptr.astype(np.int32), pat.indices.astype(np.int32)
     info = _lib.BandInfo()
-    rc = _lib.load().fpsq_band_analyze_bordered(n, m, rp.ctypes.data, ci.ctypes.data, int(border), None, C.byref(info))
+    rc = _lib.load().fpsq_band_analyze_bordered_cols(n, m, rp.ctypes.data, ci.ctypes.data, int(border), int(cols), None, None,
+                                                     C.byref(info))
     return None if rc != 0 else info.as_dict()
 
 

@@ -385,7 +385,38 @@ int fpsq_dense_get_info(fpsq_dense d, fpsq_dense_info *info);
  * end of row_perm.  nblocks, bandwidth_blocks, factor_bytes and chains describe the band part.  The dynamic regularisation
  * applies to the pivots of S by the rule of the pivots of B; without it a non-positive pivot of S gives the soft code 1 with
  * *info = that border row (1-based, the caller's numbering), and regularized_pivots counts the pivots of S too.  All sums
- * of the correction have a fixed order: calls are repeatable and the block entries keep their DETERMINISM contract. */
+ * of the correction have a fixed order: calls are repeatable and the block entries keep their DETERMINISM contract.
+ *
+ * LONG COLUMNS (fpsq_band_create_bordered_cols, _create_coo_bordered_cols, _analyze_bordered_cols: the bordered entries plus
+ * max_cols, 0 .. 16, anything else FPSQ_ERR_ARG; the bordered entries ARE these with max_cols = 0).  The transposed case: a
+ * variable that appears in constraints all over the row range -- a global parameter, a free final time or step length, a
+ * scalar control, a shared design or inflow variable -- is a long COLUMN of A, and one such column makes M structurally
+ * dense whatever the row order.  Up to max_cols of them are taken out of the band instead: with A = [A_b | U] as a column
+ * partition (U: m x s, the long columns)
+ *     M = A A' + delta I = B + U U',   B = A_b A_b' + delta I (the band that is factored),
+ *     M^-1 r = y - Z w,   y = B^-1 r (the sweeps),   Z = B^-1 U,   S = I + U'Z (s x s, S >= I),   w = S^-1 (U'y).
+ * A factorisation also forms U ([m][16] in the stored row order), Z (one tile of the block sweeps) and the Cholesky of S;
+ * every M-solve of every entry below takes the correction behind its sweeps (two launches more).  SCOPE: a handle takes ONE
+ * kind of border, max_border > 0 together with max_cols > 0 is FPSQ_ERR_ARG; at most 16 columns.
+ * SELECTION, deterministic, the row border's rule transposed: the candidates are the max_cols columns with the most entries
+ * (ties: the lower column index first), taken most first; the long columns are the SHORTEST such prefix after whose removal
+ * (a) no row of A is left without an entry (B would be structurally singular at delta = 0) and (b) the remaining columns,
+ * put through the ordering described above, have a half bandwidth in blocks of at most a quarter of the half bandwidth
+ * ALL columns give.  No such prefix: border_cols = 0 and the handle is the one max_cols = 0 gives, bit for bit.  Columns
+ * are not renumbered: every n-vector stays in the caller's order.  nblocks, bandwidth_blocks, factor_bytes and chains
+ * describe B; row_perm is the ordering of the rows on the remaining columns.
+ * PRODUCTS: A x reads a long column's entries where they are, in the rows.  In A'q no lane group walks a long column: the
+ * transposed structure holds, for long column i, one entry of value 1 per chunk of rows, pointing at a slot behind the
+ * padded rows of the vector, and a grid-wide reduction in a fixed order leaves the chunk sums of U[.][i] q[.] in those slots
+ * (fpsq_band_jac_mul(trans = 1) and the A'c / A'(A v) terms).  For the SOLUTIONS of the M-solves the slots receive w itself:
+ * U'(y - Z w) = w exactly, so the rows of A'q1 / A'q2 (hence of p1, p2, gs, Hv ...) that belong to long columns equal the
+ * products only to rounding.
+ * NUMERICS: the low-rank form is as accurate as a Cholesky of M while U is moderate against B; where the long columns
+ * dominate it loses digits roughly like cond(B) cond(S) (a numpy model of the scheme against a dense LU of K: 2e-15 .. 6e-14
+ * on the shapes of the tests where the Cholesky of M gives 1e-15 .. 7e-15; 1e-10 against 1.4e-13 on aug2dc_like(51), delta =
+ * 0, with 4 all-row columns scaled by 30, cond(B) = 1e3, cond(M) = 2e5, cond(S) = 9e3).  That loss belongs to the scheme;
+ * border_pivot_ratio reports it per factorisation.  A pivot of S that fails the rule of the pivots of B (S >= I, so only behind a
+ * failing pivot of B, which keeps *info) is regularised or reported as the last stored row; regularized_pivots counts it. */
 typedef struct fpsq_band_s *fpsq_band;
 typedef struct {
   int64_t n, m, nnz;
@@ -398,7 +429,11 @@ typedef struct {
                                 order of the two elimination chains) */
   int64_t chains;            /* 2: the band is eliminated from both ends at once (two streams), 1: one chain */
   int64_t border_rows;       /* rows eliminated last as a border (0 unless created with max_border > 0 and rows were taken) */
-  double last_border_ms;     /* device time of C, D, Z, S and its Cholesky in the last factorisation (not in last_chol_ms) */
+  double last_border_ms;     /* device time of C, D, Z, S (long columns: U, Z, S) and its Cholesky in the last factorisation
+                                (not in last_chol_ms) */
+  int64_t border_cols;       /* long columns taken out of the band (0 unless created with max_cols > 0 and columns were taken) */
+  double border_pivot_ratio; /* long columns: (largest / smallest pivot of the Cholesky factor of S)^2 in the last
+                                factorisation, an estimate of cond(S); 1 without long columns */
 } fpsq_band_info;
 int fpsq_band_create(fpsq_band *out, int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind, int32_t device);
 int fpsq_band_create_bordered(fpsq_band *out, int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind,
@@ -411,6 +446,11 @@ int fpsq_band_create_coo(fpsq_band *out, int64_t n, int64_t m, int64_t nnz, cons
                          int32_t index_base, int32_t device);
 int fpsq_band_create_coo_bordered(fpsq_band *out, int64_t n, int64_t m, int64_t nnz, const int64_t *rows, const int64_t *cols,
                                   int32_t index_base, int32_t max_border, int32_t device);
+int fpsq_band_create_bordered_cols(fpsq_band *out, int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind,
+                                   int32_t max_border, int32_t max_cols, int32_t device);
+int fpsq_band_create_coo_bordered_cols(fpsq_band *out, int64_t n, int64_t m, int64_t nnz, const int64_t *rows,
+                                       const int64_t *cols, int32_t index_base, int32_t max_border, int32_t max_cols,
+                                       int32_t device);
 int fpsq_band_factorize_coo(fpsq_band b, const double *vals, double delta, int32_t *info);
 /* the ordering decisions of fpsq_band_create alone, on the host (no device needed; rowptr / colind in HOST memory): row_perm
  * (m entries, may be null) = the caller's row stored at each position, info = blocks / half bandwidth / factor bytes /
@@ -419,6 +459,9 @@ int fpsq_band_analyze(int64_t n, int64_t m, const int32_t *rowptr, const int32_t
                       fpsq_band_info *info);
 int fpsq_band_analyze_bordered(int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind, int32_t max_border,
                                int32_t *row_perm, fpsq_band_info *info);
+/* long_cols (16 entries, may be null): the columns taken, ascending, -1 beyond border_cols */
+int fpsq_band_analyze_bordered_cols(int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind, int32_t max_border,
+                                    int32_t max_cols, int32_t *row_perm, int32_t *long_cols, fpsq_band_info *info);
 int fpsq_band_destroy(fpsq_band b);
 const char *fpsq_band_last_error(fpsq_band b);
 int fpsq_band_set_regularization(fpsq_band b, double tol, double reg);
