@@ -127,6 +127,9 @@ SYMBOLS = [
     ("fpsq_band_create_bordered_cols", C.c_int, [C.POINTER(_VP), _I64, _I64, _DP, _DP, _I32, _I32, _I32]),
     ("fpsq_band_create_coo_bordered_cols", C.c_int, [C.POINTER(_VP), _I64, _I64, _I64, _DP, _DP, _I32, _I32, _I32, _I32]),
     ("fpsq_band_analyze_bordered_cols", C.c_int, [_I64, _I64, _DP, _DP, _I32, _I32, _DP, _DP, C.POINTER(BandInfo)]),
+    ("fpsq_band_create_arrow", C.c_int, [C.POINTER(_VP), _I64, _I64, _DP, _DP, _I32, _I32, _I32]),
+    ("fpsq_band_create_coo_arrow", C.c_int, [C.POINTER(_VP), _I64, _I64, _I64, _DP, _DP, _I32, _I32, _I32, _I32]),
+    ("fpsq_band_analyze_arrow", C.c_int, [_I64, _I64, _DP, _DP, _I32, _I32, _DP, _DP, C.POINTER(BandInfo)]),
     ("fpsq_band_destroy", C.c_int, [_VP]),
     ("fpsq_band_last_error", C.c_char_p, [_VP]),
     ("fpsq_band_set_regularization", C.c_int, [_VP, _D, _D]),

@@ -50,11 +50,11 @@ struct fpsq_band_s : DirectCore {
   int bd_grid = 1;
   hipEvent_t evS0 = nullptr, evS1 = nullptr;  // around the border's share of a factorisation (last_border_ms)
   // long columns (fpsq_band_create_bordered_cols; kernels and algebra: fpsq_band.hip.h "long columns"): `cols` columns of A are
-  // kept out of the band.  bd_c / bd_z hold U and Z = B^-1 U, bd_l the factor of S, bd_part the partials; vrows = 16 bd_grid
+  // kept out of the band.  bc_c / bc_z hold U and Z = B^-1 U, bc_l the factor of S, bc_part the partials; vrows = 16 bc_grid
   // virtual rows lie behind row mpad of r2, r16, bd_keep and blk_keep.  t_nnz: entries of the transposed structure (a long
-  // column has bd_grid of them, of value vals[nnz] = 1).  lc_*: the entries of the long columns, column by column (stored
+  // column has bc_grid of them, of value vals[nnz] = 1).  lc_*: the entries of the long columns, column by column (stored
   // row, stored entry).  bd_keep: the `keep` operand of an evaluation, resp. the x of a transposed product, [mpad + vrows].
-  // bd_t[256]: (largest / smallest pivot of S)^2.  fb_*: the CSR of A_b alone for k_band_form (form_gen = 1), fb_perm its
+  // bc_t[256]: (largest / smallest pivot of S)^2.  fb_*: the CSR of A_b alone for k_band_form (form_gen = 1), fb_perm its
   // entries among the stored ones
   int cols = 0;
   int64_t t_nnz = 0, fb_nnz = 0;
@@ -62,6 +62,15 @@ struct fpsq_band_s : DirectCore {
   double* bd_keep = nullptr;
   int32_t *fb_rowptr = nullptr, *fb_colind = nullptr, *fb_perm = nullptr;
   double* fb_vals = nullptr;
+  // the long columns' own set, so that a handle can carry both kinds (the rows keep bd_*): bc_c / bc_z: U and Z_c, [mpad][16];
+  // bc_l: the factor of S_c; bc_part: [bc_grid][256]; bc_t: [256] unused slots of a reduction, then the pivot ratio; bc_grid:
+  // workgroups of the columns' reductions, over all m rows (vrows = 16 bc_grid).  ARROW (fpsq_band_create_arrow, border > 0 and
+  // cols > 0; fpsq_band.hip.h "arrow band"): lc_cols: the long columns, ascending; bc_g: G = U_s' - U_b'Z_r, [16][16];
+  // behind bc_part's [bc_grid][256] the rows' partials of the fused reduction, [bd_grid][256]; arrow_fused: FPSQ_ARROW_FUSED (default 1)
+  double *bc_c = nullptr, *bc_z = nullptr, *bc_l = nullptr, *bc_part = nullptr, *bc_t = nullptr, *bc_g = nullptr;
+  int bc_grid = 1;
+  int32_t* lc_cols = nullptr;
+  bool arrow_fused = true;
   fpsq_band_info info{};
 };
 
@@ -415,6 +424,188 @@ std::string band_order_cols(int64_t n, int64_t m, std::vector<int32_t>& rp, std:
   return msg;
 }
 
+// The ordering of an ARROW handle: at most max_border border rows AND at most max_cols long columns (include/fpsq.h, "ARROW
+// BAND", has the rule).  1: Cc = the max_cols columns with the most entries, Rc = the max_border rows of widest span over the
+// columns not in Cc.  2: the column rule on the rows not in Rc (baseline and trials), rule (a) over all rows: L.  3: the row
+// rule on the columns not in L: R.  4: L empty -> band_order, R empty -> band_order_cols, either maximum 0 -> the other rule.
+// Both taken: the band rows as step 3 ordered them, every row with all its entries, then the rows of R ascending.
+std::string band_order_arrow(int64_t n, int64_t m, std::vector<int32_t>& rp, std::vector<int32_t>& ci,
+                             std::vector<int32_t>& rperm_h, std::vector<int32_t>& vperm_h, int& chain_safe, int& chain_bw,
+                             int max_border, int max_cols, int& border, std::vector<int32_t>& lcols) {
+  border = 0;
+  lcols.clear();
+  if (max_cols <= 0) return band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, border);
+  if (max_border <= 0) return band_order_cols(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_cols, lcols);
+  const int64_t nnz = rp[m];
+  bool valid = m >= 2 && n >= 2;
+  for (int64_t i = 0; i < m && valid; ++i) {
+    valid = rp[i + 1] >= rp[i] && rp[i + 1] <= nnz;
+    for (int32_t k = rp[i]; valid && k < rp[i + 1]; ++k) valid = ci[k] >= 0 && ci[k] < n;
+  }
+  if (!valid)  // (band_order reports a bad pattern; with fewer than two rows or columns no column is taken)
+    return band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, border);
+  const std::vector<int32_t> rp0 = rp, ci0 = ci;
+  // the rows not in skip_row (null: all rows) on the columns not in drop_col, in the caller's order: CSR, the rows' and the
+  // entries' numbers among the caller's
+  struct Sub { std::vector<int32_t> rows, rp, ci, ent; };
+  auto sub_pattern = [&](const std::vector<char>* skip_row, const std::vector<char>& drop_col) {
+    Sub u;
+    u.rp.assign(1, 0);
+    for (int64_t i = 0; i < m; ++i) {
+      if (skip_row && (*skip_row)[i]) continue;
+      u.rows.push_back((int32_t)i);
+      for (int32_t t = rp0[i]; t < rp0[i + 1]; ++t)
+        if (!drop_col[ci0[t]]) {
+          u.ci.push_back(ci0[t]);
+          u.ent.push_back(t);
+        }
+      u.rp.push_back((int32_t)u.ci.size());
+    }
+    u.ci.resize(std::max<size_t>(u.ci.size(), 1));
+    return u;
+  };
+  // band_order_rows on such a pattern: the half bandwidth in blocks, -1 when the ordering fails
+  auto ordered_blocks = [&](Sub& u, std::vector<int32_t>& rperm_b, int& cs, int& cb) -> int64_t {
+    std::vector<int32_t> vperm_b;
+    rperm_b.clear();
+    const int64_t rows = (int64_t)u.rows.size();
+    if (!band_order_rows(n, rows, u.rp, u.ci, rperm_b, vperm_b, cs, cb).empty()) return -1;
+    return band_blocks(n, rows, u.rp, u.ci);
+  };
+  // 1: the candidates
+  std::vector<int64_t> cnt(n, 0);
+  for (int64_t k = 0; k < nnz; ++k) cnt[ci0[k]]++;
+  std::vector<int32_t> ccand(n);
+  for (int64_t c = 0; c < n; ++c) ccand[c] = (int32_t)c;
+  const int64_t nccand = std::min<int64_t>(max_cols, n - 1);
+  std::partial_sort(ccand.begin(), ccand.begin() + nccand, ccand.end(),
+                    [&](int32_t a, int32_t b) { return cnt[a] != cnt[b] ? cnt[a] > cnt[b] : a < b; });
+  std::vector<char> in_cc(n, 0);
+  for (int64_t k = 0; k < nccand; ++k) in_cc[ccand[k]] = 1;
+  // the max_border rows of widest span over the columns without `drop`, widest first
+  auto row_candidates = [&](const std::vector<char>& drop, std::vector<int32_t>& cand) {
+    std::vector<int64_t> span(m, 0);
+    for (int64_t i = 0; i < m; ++i) {
+      int32_t lo = INT32_MAX, hi = -1;
+      for (int32_t k = rp0[i]; k < rp0[i + 1]; ++k) {
+        if (drop[ci0[k]]) continue;
+        lo = std::min(lo, ci0[k]);
+        hi = std::max(hi, ci0[k]);
+      }
+      span[i] = hi >= 0 ? (int64_t)hi - lo + 1 : 0;
+    }
+    cand.resize(m);
+    for (int64_t i = 0; i < m; ++i) cand[i] = (int32_t)i;
+    const int64_t nc = std::min<int64_t>(max_border, m - 1);
+    std::partial_sort(cand.begin(), cand.begin() + nc, cand.end(),
+                      [&](int32_t a, int32_t b) { return span[a] != span[b] ? span[a] > span[b] : a < b; });
+    cand.resize(nc);
+  };
+  std::vector<int32_t> rcand;
+  row_candidates(in_cc, rcand);
+  std::vector<char> in_rc(m, 0);
+  for (int32_t r : rcand) in_rc[r] = 1;
+  // 2: the columns, on the rows not in Rc
+  std::vector<char> is_l(n, 0);
+  int nl = 0;
+  {
+    std::vector<int32_t> rperm_b;
+    int cs = 0, cb = 0;
+    Sub base = sub_pattern(&in_rc, is_l);
+    const int64_t bwb0 = ordered_blocks(base, rperm_b, cs, cb);
+    std::vector<char> out(n, 0);
+    for (int64_t k = 1; bwb0 > 0 && k <= nccand; ++k) {
+      out[ccand[k - 1]] = 1;
+      bool empty_row = false;  // rule (a), over ALL rows
+      for (int64_t i = 0; i < m && !empty_row; ++i) {
+        bool any = false;
+        for (int32_t t = rp0[i]; t < rp0[i + 1] && !any; ++t) any = !out[ci0[t]];
+        empty_row = !any;
+      }
+      if (empty_row) break;
+      Sub trial = sub_pattern(&in_rc, out);
+      const int64_t bw = ordered_blocks(trial, rperm_b, cs, cb);
+      if (bw < 0) break;
+      if (4 * bw > bwb0) continue;
+      is_l = out;
+      nl = (int)k;
+      break;
+    }
+  }
+  auto restore = [&] {
+    rp = rp0;
+    ci = ci0;
+    rperm_h.clear();
+    vperm_h.clear();
+  };
+  if (nl == 0) {  // 4: no long columns: the row border's rule alone
+    restore();
+    return band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, border);
+  }
+  // 3: the rows, on the columns not in L
+  int nr = 0, cs_t = 0, cb_t = 0;
+  std::vector<char> in_r(m, 0);
+  std::vector<int32_t> rows_t, rperm_t;
+  {
+    std::vector<int32_t> rperm_b;
+    int cs = 0, cb = 0;
+    Sub base = sub_pattern(nullptr, is_l);
+    const int64_t bwb0 = ordered_blocks(base, rperm_b, cs, cb);
+    row_candidates(is_l, rcand);
+    std::vector<char> out(m, 0);
+    for (int64_t k = 1; bwb0 > 0 && k <= (int64_t)rcand.size(); ++k) {
+      out[rcand[k - 1]] = 1;
+      Sub trial = sub_pattern(&out, is_l);
+      const int64_t bw = ordered_blocks(trial, rperm_b, cs, cb);
+      if (bw < 0) break;
+      if (4 * bw > bwb0) continue;
+      in_r = out;
+      nr = (int)k;
+      rows_t.swap(trial.rows);
+      rperm_t.swap(rperm_b);
+      cs_t = cs;
+      cb_t = cb;
+      break;
+    }
+  }
+  if (nr == 0) {  // 4: no border rows: the column rule alone, decided again on all rows
+    restore();
+    return band_order_cols(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_cols, lcols);
+  }
+  // both: the band rows in the order of step 3, then the border rows ascending, every row with all its entries
+  const int64_t mb = m - nr;
+  std::vector<int32_t> rp2(m + 1, 0), ci2(std::max<int64_t>(nnz, 1)), rr2(m), vp2(std::max<int64_t>(nnz, 1));
+  int64_t p = 0;
+  auto put_row = [&](int32_t r) {
+    rr2[p] = r;
+    rp2[p + 1] = rp2[p] + (rp0[r + 1] - rp0[r]);
+    for (int32_t t = rp0[r], u = rp2[p]; t < rp0[r + 1]; ++t, ++u) {
+      ci2[u] = ci0[t];
+      vp2[u] = t;
+    }
+    ++p;
+  };
+  for (int64_t q = 0; q < mb; ++q) put_row(rows_t[rperm_t.empty() ? q : rperm_t[q]]);
+  for (int64_t i = 0; i < m; ++i)
+    if (in_r[i]) put_row((int32_t)i);
+  bool identity = true;  // (the border rows already last and the band rows kept in place: not a reordered handle)
+  for (int64_t q = 0; q < m && identity; ++q) identity = rr2[q] == (int32_t)q;
+  rp.swap(rp2);
+  ci.swap(ci2);
+  rperm_h.swap(rr2);
+  vperm_h.swap(vp2);
+  if (identity) {
+    rperm_h.clear();
+    vperm_h.clear();
+  }
+  chain_safe = cs_t;
+  chain_bw = cb_t;
+  border = nr;
+  for (int64_t c = 0; c < n; ++c)
+    if (is_l[c]) lcols.push_back((int32_t)c);
+  return std::string();
+}
+
 inline size_t blk_off(const fpsq_band b, int64_t i, int64_t j) {  // block (i, j), i - (band_w - 1) <= j <= i
   return ((size_t)i * b->band_w + (size_t)(j - i + b->band_w - 1)) * kDB * kDB;
 }
@@ -433,17 +624,43 @@ void border_correct(fpsq_band b, double* y) {
 // they hold M^-1 r = y - Z w and the virtual rows behind row mpad hold w = U'(y - Z w)
 template <int NC>
 void cols_correct(fpsq_band b, double* y) {
-  hipLaunchKernelGGL(k_border_reduce<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_c, y, (int)b->m, 0, b->bd_part,
-                     b->bd_t);
-  hipLaunchKernelGGL(k_cols_update<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_z, b->bd_l, b->bd_part, b->bd_grid, y,
+  hipLaunchKernelGGL(k_border_reduce<NC>, dim3(b->bc_grid), dim3(256), 0, b->stream, b->bc_c, y, (int)b->m, 0, b->bc_part,
+                     b->bc_t);
+  hipLaunchKernelGGL(k_cols_update<NC>, dim3(b->bc_grid), dim3(256), 0, b->stream, b->bc_z, b->bc_l, b->bc_part, b->bc_grid, y,
                      (int)b->m, (int)b->mpad);
+}
+
+// The correction of an M-solve on an ARROW handle (border rows and long columns), behind the sweeps (y as above): the fused
+// pair of fpsq_band.hip.h "arrow band", or with FPSQ_ARROW_FUSED=0 the two corrections above one after the other.  The fused
+// reduction runs on the rows' grid (band rows), the update on the columns' grid (all rows and the virtual rows); the rows'
+// partials of the fused form lie behind the columns' in bc_part
+template <int NC>
+void arrow_correct(fpsq_band b, double* y) {
+  if (!b->arrow_fused) {
+    border_correct<NC>(b, y);
+    cols_correct<NC>(b, y);
+    return;
+  }
+  double* part_r = b->bc_part + (size_t)b->bc_grid * 256;
+  hipLaunchKernelGGL(k_arrow_reduce<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_c, b->bc_c, y, (int)b->mb, b->border,
+                     part_r, b->bc_part, b->bd_t);
+  hipLaunchKernelGGL(k_arrow_update<NC>, dim3(b->bc_grid), dim3(256), 0, b->stream, b->bd_z, b->bd_l, b->bc_z, b->bc_l, b->bc_g,
+                     part_r, b->bc_part, b->bd_grid, b->bd_t, y, (int)b->mb, (int)b->m, (int)b->mpad);
+}
+
+// whichever correction the handle's kind asks for
+template <int NC>
+void band_correct(fpsq_band b, double* y) {
+  if (b->border && b->cols) return arrow_correct<NC>(b, y);
+  if (b->border) border_correct<NC>(b, y);
+  if (b->cols) cols_correct<NC>(b, y);
 }
 
 // the chunk sums of U'keep into the virtual rows of an operand the A' kernels read beside the solutions (keep: [mpad + vrows][NC])
 template <int NC>
 void cols_keep(fpsq_band b, double* keep) {
-  hipLaunchKernelGGL(k_border_reduce<NC>, dim3(b->bd_grid), dim3(256), 0, b->stream, b->bd_c, keep, (int)b->m, 0,
-                     keep + (size_t)b->mpad * NC, b->bd_t);
+  hipLaunchKernelGGL(k_border_reduce<NC>, dim3(b->bc_grid), dim3(256), 0, b->stream, b->bc_c, keep, (int)b->m, 0,
+                     keep + (size_t)b->mpad * NC, b->bc_t);
 }
 
 void band_sweeps(fpsq_band b);
@@ -452,8 +669,7 @@ void band_sweeps(fpsq_band b);
 // result in b->r2
 void band_solve(fpsq_band b) {
   band_sweeps(b);
-  if (b->border) border_correct<2>(b, b->r2);
-  if (b->cols) cols_correct<2>(b, b->r2);
+  band_correct<2>(b, b->r2);
 }
 
 // the sweeps on the band rows: b->r2 <- B^-1 b->r2 (rows beyond the band's blocks are not touched)
@@ -540,7 +756,7 @@ struct BandSymbolic {
 // A A' + delta I is a band whose half width is the largest row distance of two entries of one column of A.  Reads the
 // caller's CSR (host or device memory); returns an error text, empty on success.
 std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int max_border, int max_cols,
-                          BandSymbolic& sy) {
+                          bool arrow, BandSymbolic& sy) {
   std::vector<int32_t>&rp = sy.rp, &ci = sy.ci;
   rp.resize(m + 1);
   if (hipMemcpy(rp.data(), rowptr, (size_t)(m + 1) * 4, hipMemcpyDefault) != hipSuccess || rp[0] != 0)
@@ -549,9 +765,13 @@ std::string band_symbolic(int64_t n, int64_t m, const int32_t* rowptr, const int
   ci.resize(std::max<int64_t>(nnz, 1));
   if (nnz > 0 && (!colind || hipMemcpy(ci.data(), colind, (size_t)nnz * 4, hipMemcpyDefault) != hipSuccess))
     return "fpsq_band_create: cannot read colind";
+  for (int64_t i = 0; arrow && i < m; ++i)
+    if (rp[i + 1] < rp[i] || rp[i + 1] > nnz) return "fpsq_band_create: rowptr not monotone";
   const std::string msg =
-      max_cols > 0 ? band_order_cols(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_cols, sy.lcols)
-                   : band_order(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_border, sy.border);
+      arrow ? band_order_arrow(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_border, max_cols, sy.border,
+                               sy.lcols)
+      : max_cols > 0 ? band_order_cols(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_cols, sy.lcols)
+                     : band_order(n, m, rp, ci, sy.rperm, sy.vperm, sy.chain_safe, sy.chain_bw, max_border, sy.border);
   if (!msg.empty()) return msg;
   const int64_t mb = m - sy.border;
   const int ncols = (int)sy.lcols.size();
@@ -714,14 +934,20 @@ void band_upload(fpsq_band b, const BandSymbolic& sy) {
 // Non-zero (the handle is destroyed): failed.
 int cols_setup(fpsq_band b, const BandSymbolic& sy) {
   if (b->cols == 0) return FPSQ_OK;
-  b->bd_grid = sy.vgrid;
-  hipEventCreate(&b->evS0);
-  hipEventCreate(&b->evS1);
+  b->bc_grid = sy.vgrid;
+  if (!b->evS0) {  // (an arrow handle: border_setup has made them)
+    hipEventCreate(&b->evS0);
+    hipEventCreate(&b->evS1);
+  }
   const size_t tile = (size_t)b->mpad * kBlkCols, nl = std::max<size_t>(sy.lc_row.size(), 1);
-  int rc = chain16_setup(b) || dalloc(b, &b->bd_c, tile) || dalloc(b, &b->bd_z, tile) ||
-           dalloc(b, &b->bd_l, (size_t)kBorderMax * kBorderMax) || dalloc(b, &b->bd_part, (size_t)b->bd_grid * 256) ||
-           dalloc(b, &b->bd_t, 256 + 8) || dalloc(b, &b->bd_keep, (size_t)(b->mpad + b->vrows)) ||
+  // (an arrow handle keeps the rows' partials of the fused reduction behind the columns')
+  const size_t parts = (size_t)b->bc_grid * 256 + (b->border ? (size_t)b->bd_grid * 256 : 0);
+  int rc = chain16_setup(b) || dalloc(b, &b->bc_c, tile) || dalloc(b, &b->bc_z, tile) ||
+           dalloc(b, &b->bc_l, (size_t)kBorderMax * kBorderMax) || dalloc(b, &b->bc_part, parts) ||
+           dalloc(b, &b->bc_t, 256 + 8) || dalloc(b, &b->bd_keep, (size_t)(b->mpad + b->vrows)) ||
            dalloc(b, &b->lc_ptr, (size_t)b->cols + 1) || dalloc(b, &b->lc_row, nl) || dalloc(b, &b->lc_ent, nl);
+  if (!rc && b->border)
+    rc = dalloc(b, &b->bc_g, (size_t)kBorderMax * kBorderMax) || dalloc(b, &b->lc_cols, (size_t)kBorderMax);
   if (!rc && b->form_gen == 1) {
     b->fb_nnz = (int64_t)sy.perm_b.size();
     const size_t fz = (size_t)std::max<int64_t>(b->fb_nnz, 1);
@@ -735,6 +961,7 @@ int cols_setup(fpsq_band b, const BandSymbolic& sy) {
   }
   hipMemset(b->bd_keep, 0, (size_t)(b->mpad + b->vrows) * 8);
   hipMemcpy(b->lc_ptr, sy.lc_ptr.data(), ((size_t)b->cols + 1) * 4, hipMemcpyHostToDevice);
+  if (b->border) hipMemcpy(b->lc_cols, sy.lcols.data(), (size_t)b->cols * 4, hipMemcpyHostToDevice);
   if (!sy.lc_row.empty()) {
     hipMemcpy(b->lc_row, sy.lc_row.data(), sy.lc_row.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(b->lc_ent, sy.lc_ent.data(), sy.lc_ent.size() * 4, hipMemcpyHostToDevice);
@@ -751,20 +978,28 @@ int cols_setup(fpsq_band b, const BandSymbolic& sy) {
 }
 
 // The long columns' share of a factorisation, behind the band's Cholesky on b->stream: U scattered from the current values,
-// Z = B^-1 U by the 16-column sweeps, the partials of U'Z, S = I + U'Z and its Cholesky
+// Z = B^-1 U by the 16-column sweeps, the partials of U'Z, S = I + U'Z and its Cholesky.  On an arrow handle it runs behind
+// border_factor: U covers the border rows too, Z_c = M_r^-1 U takes the rows' correction behind the sweeps, and G is formed
 void cols_factor(fpsq_band b) {
   hipStream_t s = b->stream;
   const size_t tile = (size_t)b->mpad * kBlkCols * 8;
-  hipEventRecord(b->evS0, s);
-  hipMemsetAsync(b->bd_c, 0, tile, s);
-  hipLaunchKernelGGL(k_cols_scatter, dim3(b->cols, 64), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->vals, b->bd_c);
-  hipMemcpyAsync(b->r16, b->bd_c, tile, hipMemcpyDeviceToDevice, s);
+  if (!b->border) hipEventRecord(b->evS0, s);  // (an arrow handle: border_factor, which runs first, has recorded it)
+  hipMemsetAsync(b->bc_c, 0, tile, s);
+  hipLaunchKernelGGL(k_cols_scatter, dim3(b->cols, 64), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->vals, b->bc_c);
+  if (b->border) {  // G = U_s' - U_b'Z_r for the fused correction
+    hipLaunchKernelGGL(k_border_reduce<kBlkCols>, dim3(b->bc_grid), dim3(256), 0, s, b->bc_c, b->bd_z, (int)b->mb, 0, b->bc_part,
+                       b->bc_t);
+    hipLaunchKernelGGL(k_arrow_g, dim3(1), dim3(256), 0, s, b->bc_part, b->bc_grid, b->bc_c, (int)b->mb, b->border, b->cols,
+                       b->bc_g);
+  }
+  hipMemcpyAsync(b->r16, b->bc_c, tile, hipMemcpyDeviceToDevice, s);
   chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
-  hipMemcpyAsync(b->bd_z, b->r16, tile, hipMemcpyDeviceToDevice, s);
-  hipLaunchKernelGGL(k_border_reduce<kBlkCols>, dim3(b->bd_grid), dim3(256), 0, s, b->bd_c, b->bd_z, (int)b->m, 0, b->bd_part,
-                     b->bd_t);
-  hipLaunchKernelGGL(k_cols_chol, dim3(1), dim3(256), 0, s, b->bd_part, b->bd_grid, b->cols, (int)b->m, b->piv_tol, b->piv_reg,
-                     b->bd_l, b->bd_t + 256, b->info_dev);
+  if (b->border) border_correct<kBlkCols>(b, b->r16);  // (Z_c = M_r^-1 U: the rows' correction behind the sweeps)
+  hipMemcpyAsync(b->bc_z, b->r16, tile, hipMemcpyDeviceToDevice, s);
+  hipLaunchKernelGGL(k_border_reduce<kBlkCols>, dim3(b->bc_grid), dim3(256), 0, s, b->bc_c, b->bc_z, (int)b->m, 0, b->bc_part,
+                     b->bc_t);
+  hipLaunchKernelGGL(k_cols_chol, dim3(1), dim3(256), 0, s, b->bc_part, b->bc_grid, b->cols, (int)b->m, b->piv_tol, b->piv_reg,
+                     b->bc_l, b->bc_t + 256, b->info_dev);
   hipEventRecord(b->evS1, s);
 }
 
@@ -795,6 +1030,8 @@ void border_factor(fpsq_band b, double delta) {
   hipEventRecord(b->evS0, s);
   hipMemsetAsync(b->blk_xg, 0, (size_t)b->n * kBlkCols * 8, s);
   hipLaunchKernelGGL(k_border_scatter, dim3(b->border), dim3(256), 0, s, b->rowptr, b->colind, b->vals, mb, b->blk_xg);
+  if (b->cols)  // (arrow: [C; D - delta I] = A_o A_s,o', the long columns belong to U)
+    hipLaunchKernelGGL(k_arrow_clear, dim3(1), dim3(256), 0, s, b->lc_cols, b->cols, b->blk_xg);
   const int lgA = lane_group(b->nnz, b->m);
   WITH_LANE_GROUP(lgA, hipLaunchKernelGGL(k_bqb_prologue<LG>, dim3((unsigned)std::min<int64_t>(
                                               (b->mpad + 256 / lgA - 1) / (256 / lgA), 2048)), dim3(256), 0, s, b->rowptr,
@@ -806,16 +1043,23 @@ void border_factor(fpsq_band b, double delta) {
                      b->bd_t);
   hipLaunchKernelGGL(k_border_chol, dim3(1), dim3(256), 0, s, b->bd_part, b->bd_grid, b->bd_c, mb, b->border, delta, b->piv_tol,
                      b->piv_reg, b->bd_l, b->info_dev);
-  hipEventRecord(b->evS1, s);
+  if (!b->cols) hipEventRecord(b->evS1, s);  // (an arrow handle: cols_factor, which runs next, records it)
 }
 
 // the check of max_cols every entry that takes it makes before anything else: null = fine
-const char* bad_max_cols(int32_t max_border, int32_t max_cols) {
+const char* bad_max_cols(int32_t max_border, int32_t max_cols, bool arrow) {
   if (max_cols < 0 || max_cols > kBorderMax) return "max_cols must be 0 .. 16";
-  if (max_border > 0 && max_cols > 0)
+  if (!arrow && max_border > 0 && max_cols > 0)
     return "max_border > 0 together with max_cols > 0: a handle takes one kind of border, rows or columns";
   return nullptr;
 }
+
+int band_analyze(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border, int32_t max_cols,
+                 bool arrow, int32_t* row_perm, int32_t* long_cols, fpsq_band_info* info);
+int band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border,
+                int32_t max_cols, bool arrow, int32_t device);
+int band_create_coo(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
+                    int32_t index_base, int32_t max_border, int32_t max_cols, bool arrow, int32_t device);
 }  // namespace
 
 extern "C" {
@@ -834,11 +1078,23 @@ int fpsq_band_analyze_bordered(int64_t n, int64_t m, const int32_t* rowptr, cons
 
 int fpsq_band_analyze_bordered_cols(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border,
                                     int32_t max_cols, int32_t* row_perm, int32_t* long_cols, fpsq_band_info* info) {
+  return band_analyze(n, m, rowptr, colind, max_border, max_cols, false, row_perm, long_cols, info);
+}
+
+int fpsq_band_analyze_arrow(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border,
+                            int32_t max_cols, int32_t* row_perm, int32_t* long_cols, fpsq_band_info* info) {
+  return band_analyze(n, m, rowptr, colind, max_border, max_cols, true, row_perm, long_cols, info);
+}
+}  // extern "C"
+
+namespace {
+int band_analyze(int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border, int32_t max_cols,
+                 bool arrow, int32_t* row_perm, int32_t* long_cols, fpsq_band_info* info) {
   if (max_border < 0 || max_border > kBorderMax) {
     g_band_create_error = "fpsq_band_analyze: max_border must be 0 .. 16";
     return FPSQ_ERR_ARG;
   }
-  if (const char* what = bad_max_cols(max_border, max_cols)) {
+  if (const char* what = bad_max_cols(max_border, max_cols, arrow)) {
     g_band_create_error = std::string("fpsq_band_analyze: ") + what;
     return FPSQ_ERR_ARG;
   }
@@ -861,9 +1117,10 @@ int fpsq_band_analyze_bordered_cols(int64_t n, int64_t m, const int32_t* rowptr,
   ci.resize(std::max<int64_t>(nnz, 1));
   int chain_safe = 0, chain_bw = 0, border = 0;
   std::vector<int32_t> lcols;
-  const std::string msg = max_cols > 0
-                              ? band_order_cols(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_cols, lcols)
-                              : band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, border);
+  const std::string msg =
+      arrow ? band_order_arrow(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, max_cols, border, lcols)
+      : max_cols > 0 ? band_order_cols(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_cols, lcols)
+                     : band_order(n, m, rp, ci, rperm_h, vperm_h, chain_safe, chain_bw, max_border, border);
   if (!msg.empty()) {
     g_band_create_error = msg;
     return FPSQ_ERR_ARG;
@@ -901,6 +1158,9 @@ int fpsq_band_analyze_bordered_cols(int64_t n, int64_t m, const int32_t* rowptr,
   }
   return FPSQ_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int fpsq_band_destroy(fpsq_band b) {
   if (!b) return FPSQ_ERR_ARG;
@@ -929,11 +1189,23 @@ int fpsq_band_create_bordered(fpsq_band* out, int64_t n, int64_t m, const int32_
 
 int fpsq_band_create_bordered_cols(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind,
                                    int32_t max_border, int32_t max_cols, int32_t device) {
+  return band_create(out, n, m, rowptr, colind, max_border, max_cols, false, device);
+}
+
+int fpsq_band_create_arrow(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind,
+                           int32_t max_border, int32_t max_cols, int32_t device) {
+  return band_create(out, n, m, rowptr, colind, max_border, max_cols, true, device);
+}
+}  // extern "C"
+
+namespace {
+int band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, const int32_t* colind, int32_t max_border,
+                int32_t max_cols, bool arrow, int32_t device) {
   if (max_border < 0 || max_border > kBorderMax) {
     g_band_create_error = "fpsq_band_create: max_border must be 0 .. 16";
     return FPSQ_ERR_ARG;
   }
-  if (const char* what = bad_max_cols(max_border, max_cols)) {
+  if (const char* what = bad_max_cols(max_border, max_cols, arrow)) {
     g_band_create_error = std::string("fpsq_band_create: ") + what;
     return FPSQ_ERR_ARG;
   }
@@ -953,7 +1225,7 @@ int fpsq_band_create_bordered_cols(fpsq_band* out, int64_t n, int64_t m, const i
     return FPSQ_ERR_HIP;
   }
   BandSymbolic sy;
-  const std::string msg = band_symbolic(n, m, rowptr, colind, max_border, max_cols, sy);
+  const std::string msg = band_symbolic(n, m, rowptr, colind, max_border, max_cols, arrow, sy);
   if (!msg.empty()) {
     g_band_create_error = msg;
     return FPSQ_ERR_ARG;
@@ -977,6 +1249,7 @@ int fpsq_band_create_bordered_cols(fpsq_band* out, int64_t n, int64_t m, const i
   b->chain_bw = std::min(sy.chain_bw, (b->band_w - 1) / 2);
   b->reordered = !sy.rperm.empty();
   b->rperm_host = sy.rperm;
+  if (const char* ev = std::getenv("FPSQ_ARROW_FUSED")) b->arrow_fused = std::atoi(ev) != 0;
   if (int rc = band_choose_form(b)) return rc;
   if (int rc = band_alloc(b)) return rc;
   band_upload(b, sy);
@@ -1010,6 +1283,9 @@ int fpsq_band_create_bordered_cols(fpsq_band* out, int64_t n, int64_t m, const i
   *out = b;
   return FPSQ_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int fpsq_band_create_coo(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
                          int32_t index_base, int32_t device) {
@@ -1024,11 +1300,23 @@ int fpsq_band_create_coo_bordered(fpsq_band* out, int64_t n, int64_t m, int64_t 
 int fpsq_band_create_coo_bordered_cols(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows,
                                        const int64_t* cols, int32_t index_base, int32_t max_border, int32_t max_cols,
                                        int32_t device) {
+  return band_create_coo(out, n, m, nnz, rows, cols, index_base, max_border, max_cols, false, device);
+}
+
+int fpsq_band_create_coo_arrow(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
+                               int32_t index_base, int32_t max_border, int32_t max_cols, int32_t device) {
+  return band_create_coo(out, n, m, nnz, rows, cols, index_base, max_border, max_cols, true, device);
+}
+}  // extern "C"
+
+namespace {
+int band_create_coo(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
+                    int32_t index_base, int32_t max_border, int32_t max_cols, bool arrow, int32_t device) {
   if (max_border < 0 || max_border > kBorderMax) {
     g_band_create_error = "fpsq_band_create_coo: max_border must be 0 .. 16";
     return FPSQ_ERR_ARG;
   }
-  if (const char* what = bad_max_cols(max_border, max_cols)) {
+  if (const char* what = bad_max_cols(max_border, max_cols, arrow)) {
     g_band_create_error = std::string("fpsq_band_create_coo: ") + what;
     return FPSQ_ERR_ARG;
   }
@@ -1056,7 +1344,7 @@ int fpsq_band_create_coo_bordered_cols(fpsq_band* out, int64_t n, int64_t m, int
   std::vector<int32_t> rp(m + 1, 0);
   for (int64_t i = 0; i < ns; ++i) rp[srow[i] + 1]++;
   for (int64_t i = 0; i < m; ++i) rp[i + 1] += rp[i];
-  if (int rc = fpsq_band_create_bordered_cols(out, n, m, rp.data(), scol.data(), max_border, max_cols, device)) return rc;
+  if (int rc = band_create(out, n, m, rp.data(), scol.data(), max_border, max_cols, arrow, device)) return rc;
   fpsq_band b = *out;
   const bool dup = ns != nnz;
   if (dalloc(b, &b->coo_perm, (size_t)std::max<int64_t>(nnz, 1)) || dalloc(b, &b->coo_in, (size_t)std::max<int64_t>(nnz, 1)) ||
@@ -1072,6 +1360,9 @@ int fpsq_band_create_coo_bordered_cols(fpsq_band* out, int64_t n, int64_t m, int
   b->coo_nnz = nnz;
   return FPSQ_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int fpsq_band_factorize_coo(fpsq_band b, const double* vals, double delta, int32_t* info) {
   if (!b || b->coo_nnz < 0 || (!vals && b->coo_nnz > 0)) {
@@ -1167,7 +1458,7 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
       hipEventElapsedTime(&ms, b->evS0, b->evS1);
       b->info.last_border_ms = ms;
       b->info.last_chol_ms -= ms;  // (the band's Cholesky alone, as on a handle without a border)
-      if (b->cols) CHK(b, hipMemcpy(&b->info.border_pivot_ratio, b->bd_t + 256, 8, hipMemcpyDeviceToHost));
+      if (b->cols) CHK(b, hipMemcpy(&b->info.border_pivot_ratio, b->bc_t + 256, 8, hipMemcpyDeviceToHost));
       if (expired) {
         b->factored = false;
         b->err = "band_factorize: Z = B^-1 C did not arrive (bounded wait of the block sweep expired)";
@@ -1479,8 +1770,7 @@ int blk_setup(fpsq_band b, bool keep, bool tv) {
 // the two sweeps on the tile's right-hand sides in b->r16, the border correction included: the solutions end up in b->r16
 void blk_sweeps(fpsq_band b) {
   chain_sweeps16(b, b->Mb, b->band_w, b->chain_safe, b->chain_bw);
-  if (b->border) border_correct<kBlkCols>(b, b->r16);
-  if (b->cols) cols_correct<kBlkCols>(b, b->r16);
+  band_correct<kBlkCols>(b, b->r16);
 }
 
 // A xg into the sweeps' layout, then the two sweeps

@@ -1322,4 +1322,151 @@ __global__ __launch_bounds__(256) void k_cols_chol(const double* __restrict__ pa
   }
 }
 
+// ---- arrow band (fpsq_band_create_arrow): border rows AND long columns on one handle.  Stored order: the mb band rows, then
+// the s_r border rows; L = the s_c long columns, "o" = the other columns,
+//   M = M_r + U U',   U = [U_b; U_s] (all m rows),   M_r = [B C; C' D],  B = A_b,o A_b,o' + delta I,  C = A_b,o A_s,o',
+//   D = A_s,o A_s,o' + delta I.
+// M_r^-1 is the bordered band's solve (Z_r = B^-1 C, S_r = D - C'Z_r), the long columns' correction is wrapped around it
+// (Z_c = M_r^-1 U, S_c = I + U'Z_c).  NESTED form of an M-solve: the sweeps, k_border_reduce / k_border_update, k_border_reduce
+// / k_cols_update (four launches).  FUSED form (two launches): with y the sweeps' output and t the border's right-hand side,
+//   w_r = S_r^-1 (t - C'y),   U'M_r^-1 r = U_b'y + G w_r,   G = U_s' - U_b'Z_r (s_c x s_r, formed once per factorisation),
+//   w_c = S_c^-1 (U_b'y + G w_r),   u = y - Z_r w_r - Z_c,b w_c on the band rows,   w_r - Z_c,s w_c on the border rows,
+// so k_arrow_reduce forms the partials of C'y and of U_b'y in ONE pass over y and k_arrow_update corrects every row once.  The
+// virtual rows receive w_c as k_cols_update leaves it.  Sums in a fixed order that depends on the shape alone, column c reads
+// column c only, no atomics, no waits: the contract of the two corrections above.
+
+// xg[lcols[i]][0 .. 15] = 0: the rows of the border's scattered tile at the long columns, so that the block A product forms
+// [C; D - delta I] = A_o A_s,o' although A's rows hold the long columns' entries
+__global__ __launch_bounds__(256) void k_arrow_clear(const int32_t* __restrict__ lcols, int s_c, double* __restrict__ xg) {
+  const int i = threadIdx.x / kBlkCols, c = threadIdx.x % kBlkCols;
+  if (i < s_c) xg[(size_t)lcols[i] * kBlkCols + c] = 0.0;
+}
+
+// One workgroup: G[i][j] = U[mb + j][i] - sum of the partials of U_b'Z_r (k_border_reduce<16> with U for C and Z_r for y,
+// summed in index order), zero beyond s_c resp. s_r; [16][16] row-major
+__global__ __launch_bounds__(256) void k_arrow_g(const double* __restrict__ part, int nparts, const double* __restrict__ U, int mb,
+                                                 int s_r, int s_c, double* __restrict__ G) {
+  const int i = threadIdx.x / kBorderMax, j = threadIdx.x % kBorderMax;
+  double a = 0.0;
+  for (int q = 0; q < nparts; ++q) a += part[(size_t)q * 256 + threadIdx.x];
+  G[threadIdx.x] = i < s_c && j < s_r ? U[(size_t)(mb + j) * kBorderMax + i] - a : 0.0;
+}
+
+// partR[blk][i][c] = sum over this workgroup's band rows p of C[p][i] y[p][c], partC[blk][i][c] the same with U_b; workgroup 0
+// also saves t (tsave[i][c] = y[mb + i][c], zero for i >= s).  The slices and their order are k_border_reduce's.
+template <int NC>
+__global__ __launch_bounds__(256) void k_arrow_reduce(const double* __restrict__ Cm, const double* __restrict__ Um,
+                                                      const double* __restrict__ y, int mb, int s, double* __restrict__ partR,
+                                                      double* __restrict__ partC, double* __restrict__ tsave) {
+  constexpr int NO = kBorderMax * NC;
+  constexpr int NS = 256 / NO;
+  __shared__ double shr[256], shc[256];
+  const int o = threadIdx.x % NO, sl = threadIdx.x / NO, i = o / NC, c = o % NC;
+  const int chunk = (mb + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int lo = min(mb, (int)blockIdx.x * chunk), hi = min(mb, lo + chunk);
+  double ar = 0.0, ac = 0.0;
+  for (int p = lo + sl; p < hi; p += NS) {
+    const double v = y[(size_t)p * NC + c];
+    ar += Cm[(size_t)p * kBorderMax + i] * v;
+    ac += Um[(size_t)p * kBorderMax + i] * v;
+  }
+  if (NS > 1) {
+    shr[threadIdx.x] = ar;
+    shc[threadIdx.x] = ac;
+    __syncthreads();
+    if (sl == 0)
+      for (int q = 1; q < NS; ++q) {
+        ar += shr[q * NO + o];
+        ac += shc[q * NO + o];
+      }
+  }
+  if (sl == 0) {
+    partR[(size_t)blockIdx.x * NO + o] = ar;
+    partC[(size_t)blockIdx.x * NO + o] = ac;
+    if (blockIdx.x == 0) tsave[o] = i < s ? y[(size_t)(mb + i) * NC + c] : 0.0;
+  }
+}
+
+// g[.][c] <- L'^-1 L^-1 g[.][c] (L: [16][16] row-major, lower, identity beyond its order), the solve of the two update kernels
+template <int NC>
+__device__ __forceinline__ void arrow_solve16(const double* L, double* g, int c) {
+  double w[kBorderMax];
+#pragma unroll
+  for (int i = 0; i < kBorderMax; ++i) {
+    double v = g[i * NC + c];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v -= L[i * kBorderMax + k] * w[k];
+    w[i] = v / L[i * kBorderMax + i];
+  }
+#pragma unroll
+  for (int i = kBorderMax - 1; i >= 0; --i) {
+    double v = w[i];
+#pragma unroll
+    for (int k = i + 1; k < kBorderMax; ++k) v -= L[k * kBorderMax + i] * w[k];
+    w[i] = v / L[i * kBorderMax + i];
+  }
+#pragma unroll
+  for (int i = 0; i < kBorderMax; ++i) g[i * NC + c] = w[i];
+}
+
+// every workgroup: both sets of partials (nparts of each, the reduction's grid) re-summed in index order, w_r = S_r^-1 (t -
+// C'y), w_c = S_c^-1 (U_b'y + G w_r), then its own slice of ALL m rows (the grid is the long columns' grid, over m): band rows
+// y -= Z_r w_r + Z_c w_c, border rows y = w_r - Z_c w_c; and its own virtual rows, w_c for workgroup 0, zero for the others.
+template <int NC>
+__global__ __launch_bounds__(256) void k_arrow_update(const double* __restrict__ Zr, const double* __restrict__ Lrs,
+                                                      const double* __restrict__ Zc, const double* __restrict__ Lcs,
+                                                      const double* __restrict__ Gm, const double* __restrict__ partR,
+                                                      const double* __restrict__ partC, int nparts,
+                                                      const double* __restrict__ tsave, double* y, int mb, int m, int mpad) {
+  constexpr int NO = kBorderMax * NC;
+  __shared__ double Lr[kBorderMax * kBorderMax], Lc[kBorderMax * kBorderMax], G[kBorderMax * kBorderMax];
+  __shared__ double gr[NO], gc[NO];
+  Lr[threadIdx.x] = Lrs[threadIdx.x];
+  Lc[threadIdx.x] = Lcs[threadIdx.x];
+  G[threadIdx.x] = Gm[threadIdx.x];
+  if (threadIdx.x < NO) {
+    double a = 0.0, u = 0.0;
+    for (int q = 0; q < nparts; ++q) {
+      a += partR[(size_t)q * NO + threadIdx.x];
+      u += partC[(size_t)q * NO + threadIdx.x];
+    }
+    gr[threadIdx.x] = tsave[threadIdx.x] - a;
+    gc[threadIdx.x] = u;
+  }
+  __syncthreads();
+  if (threadIdx.x < NC) {
+    const int c = threadIdx.x;
+    arrow_solve16<NC>(Lr, gr, c);
+    for (int i = 0; i < kBorderMax; ++i) {
+      double v = gc[i * NC + c];
+#pragma unroll
+      for (int j = 0; j < kBorderMax; ++j) v += G[i * kBorderMax + j] * gr[j * NC + c];
+      gc[i * NC + c] = v;
+    }
+    arrow_solve16<NC>(Lc, gc, c);
+  }
+  __syncthreads();
+  const int chunk = (m + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int lo = min(m, (int)blockIdx.x * chunk), hi = min(m, lo + chunk);
+  for (int64_t idx = (int64_t)lo * NC + threadIdx.x; idx < (int64_t)hi * NC; idx += 256) {
+    const int64_t p = idx / NC;
+    const int c = (int)(idx % NC);
+    const double* zc = Zc + (size_t)p * kBorderMax;
+    double a = 0.0;
+#pragma unroll
+    for (int i = 0; i < kBorderMax; ++i) a += zc[i] * gc[i * NC + c];
+    if (p < mb) {
+      const double* zr = Zr + (size_t)p * kBorderMax;
+      double r = 0.0;
+#pragma unroll
+      for (int i = 0; i < kBorderMax; ++i) r += zr[i] * gr[i * NC + c];
+      y[idx] = (y[idx] - r) - a;
+    } else {
+      y[idx] = gr[(int)(p - mb) * NC + c] - a;
+    }
+  }
+  if (threadIdx.x < NO)  // (virtual row mpad + 16 blk + i, column c: blk * NO + i * NC + c behind row mpad)
+    y[(size_t)mpad * NC + (size_t)blockIdx.x * NO + threadIdx.x] = blockIdx.x == 0 ? gc[threadIdx.x] : 0.0;
+}
+
 }  // namespace fpsq

@@ -200,10 +200,12 @@ class DeviceBandEqQP:
     ldlt_tol / ldlt_r2: the dynamic regularisation of `LDLtSolver`, defaults as in qdsolver._DirectQDSolver (sqrt(eps),
     -sqrt(eps); "drop" drops a vanishing pivot).  Has the surface `fps_solve_device` uses on DeviceEqQP.
     `border`, `cols` (class attributes, 0 .. 16; DeviceBorderedBandEqQP sets them per object): the max_border / max_cols the
-    handle is created with."""
+    handle is created with.  `_create_entry` (class attribute): the C entry that creates it (DeviceArrowBandEqQP names
+    `fpsq_band_create_arrow`)."""
 
     border = 0
     cols = 0
+    _create_entry = "fpsq_band_create_bordered_cols"
 
     def __init__(self, qp, sigma=1e3, rho=1.0, delta=0.0, eta=0.0, device=0, ldlt_tol=None, ldlt_r2=None):
         from .qdsolver import _ldlt_r2
@@ -215,8 +217,8 @@ class DeviceBandEqQP:
         rp = np.ascontiguousarray(qp.rowptr, dtype=np.int32)
         ci = np.ascontiguousarray(qp.colind, dtype=np.int32)
         h = C.c_void_p()
-        if self._lib.fpsq_band_create_bordered_cols(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, int(self.border),
-                                                    int(self.cols), self.device) != 0:
+        if getattr(self._lib, self._create_entry)(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, int(self.border),
+                                                  int(self.cols), self.device) != 0:
             raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
         self._h = h
         try:
@@ -402,10 +404,25 @@ class DeviceBorderedBandEqQP(DeviceBandEqQP):
     `cols` (0 .. 16) is the transposed case: at most that many long COLUMNS -- a global parameter, a free final time, a
     scalar control -- are taken out of the band and every M-solve is corrected by a low-rank term (include/fpsq.h "LONG
     COLUMNS"); `info()["border_cols"]` says how many were taken and `info()["border_pivot_ratio"]` what the correction costs
-    in digits.  A handle takes ONE kind: pass `border=0` with `cols`.  The other keywords are DeviceBandEqQP's (whose parameter
-    list stays as it is)."""
+    in digits.  A handle of THIS class takes ONE kind: pass `border=0` with `cols`; DeviceArrowBandEqQP takes both.  The other
+    keywords are DeviceBandEqQP's (whose parameter list stays as it is)."""
 
     def __init__(self, qp, border=16, cols=0, **kwargs):
+        self.border = int(border)
+        self.cols = int(cols)
+        super().__init__(qp, **kwargs)
+
+
+class DeviceArrowBandEqQP(DeviceBandEqQP):
+    """DeviceBandEqQP on an ARROW band: at most `border` long constraint rows AND at most `cols` long columns on one handle
+    (both 0 .. 16, independently; include/fpsq.h "ARROW BAND") -- a model with a global parameter or a free final time that
+    also has an integral, mean-value or mass constraint.  Every method is the base class's; `info()["border_rows"]` and
+    `info()["border_cols"]` say what was taken (nothing of one kind: the handle is DeviceBorderedBandEqQP's of the other).
+    The other keywords are DeviceBandEqQP's."""
+
+    _create_entry = "fpsq_band_create_arrow"
+
+    def __init__(self, qp, border=16, cols=16, **kwargs):
         self.border = int(border)
         self.cols = int(cols)
         super().__init__(qp, **kwargs)

@@ -685,7 +685,8 @@ class _DevicePenalty:
 
 def fps_solve_device(dev, x0, *, atol=_SE, rtol=_SE, max_iter=100, max_time=300.0, verbose=0, **kwargs):
     """fps_solve on a device-resident equality QP (`DeviceEqQP` / `DeviceSparseHessianEqQP`: the iterative back-end, with a
-    diagonal / a sparse symmetric objective Hessian, or `DeviceBandEqQP`: the banded direct one): x0 and every iterate are torch tensors in HBM, each obj/grad! is one fpsq_qp_objgrad /
+    diagonal / a sparse symmetric objective Hessian, or `DeviceBandEqQP`: the banded direct one, `DeviceBorderedBandEqQP` / `DeviceArrowBandEqQP`
+    with long rows and / or long columns kept out of the band): x0 and every iterate are torch tensors in HBM, each obj/grad! is one fpsq_qp_objgrad /
     fpsq_band_qp_objgrad, each Hessian product of the `trunk` sub-solver one fpsq_qp_hprod / fpsq_band_qp_hprod.
     Returns ExecutionStats whose `solution` / `multipliers` are device tensors."""
     import torch

@@ -199,6 +199,12 @@ def with_long_columns(qp: EqQP, s: int, kind: str = "param", seed: int = 0) -> E
         x=np.concatenate([qp.x, xhat[n:] + 0.1 * (2.0 * uniform01(seed, idx, 4) - 1.0)]))
 
 
+def with_arrow(qp: EqQP, s_rows: int, s_cols: int, row_kind: str = "mean", col_kind: str = "param", seed: int = 0) -> EqQP:
+    """A copy of `qp` with `s_rows` long rows AND `s_cols` long columns: `with_long_columns(with_border_rows(qp, ...), ...)`, so
+    the columns reach the border rows too (U_s != 0) -- the case of include/fpsq.h "ARROW BAND".  xhat stays feasible."""
+    return with_long_columns(with_border_rows(qp, s_rows, kind=row_kind, seed=seed), s_cols, kind=col_kind, seed=seed)
+
+
 def _stratified_rows(m, n, per_row, start, width, seed, diag_col=None, diag_boost=0.0):
     """Each of the m rows gets `per_row` sorted, distinct columns: one per stratum of
     [start[i], start[i] + width).  If diag_col is given, the stratum containing diag_col[i] is

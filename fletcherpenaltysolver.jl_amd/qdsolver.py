@@ -350,6 +350,26 @@ class HIPBandedDirectQDSolver(_DirectQDSolver):
 qdsolver_correspondence["hip_ldlt"] = HIPBandedDirectQDSolver
 
 
+class HIPArrowBandedDirectQDSolver(HIPBandedDirectQDSolver):
+    """HIPBandedDirectQDSolver with border rows AND long columns on one handle (include/fpsq.h "ARROW BAND"): at most `border`
+    long constraint rows and at most `cols` long columns, both 0 .. 16, independently; `info()["border_rows"]` and
+    `info()["border_cols"]` say what was taken."""
+
+    def __init__(self, nlp, _zero=0.0, *, border=16, cols=16, **kwargs):
+        super().__init__(nlp, _zero, border=border, cols=cols, **kwargs)
+
+    def _create(self, rows, cols, device):
+        b = C.c_void_p()
+        rc = self._lib.fpsq_band_create_coo_arrow(C.byref(b), self.nvar, self.ncon, rows.size, rows.ctypes.data,
+                                                  cols.ctypes.data, 1, self.border, self.cols, device)
+        if rc != 0:
+            raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
+        self._h = b
+
+
+qdsolver_correspondence["hip_ldlt_arrow"] = HIPArrowBandedDirectQDSolver
+
+
 # ---------------------------------------------------------------------------------------------- back-end selection
 
 AUTO_MAX_BAND_BLOCKS = 4    # half bandwidth of M = A A' + delta I (in 128-row blocks) up to which "auto" goes direct
@@ -360,6 +380,16 @@ def band_analysis(nlp, explicit_linear_constraints=False, border=0, cols=0):
     """The symbolic phase alone (fpsq_band_analyze_bordered_cols: host only, no device): blocks / half bandwidth / factor
     bytes / reordered / chains / border rows / long columns of the block-banded structure
     `HIPBandedDirectQDSolver(..., border=border, cols=cols)` would set up for this model's Jacobian pattern."""
+    return _band_analysis(nlp, explicit_linear_constraints, border, cols, "fpsq_band_analyze_bordered_cols")
+
+
+def band_analysis_arrow(nlp, explicit_linear_constraints=False, border=16, cols=16):
+    """The same for `HIPArrowBandedDirectQDSolver(..., border=border, cols=cols)` (fpsq_band_analyze_arrow): border rows and
+    long columns on one handle."""
+    return _band_analysis(nlp, explicit_linear_constraints, border, cols, "fpsq_band_analyze_arrow")
+
+
+def _band_analysis(nlp, explicit_linear_constraints, border, cols, entry):
     import scipy.sparse as sp
 
     if explicit_linear_constraints:
@@ -372,8 +402,7 @@ def band_analysis(nlp, explicit_linear_constraints=False, border=0, cols=0):
     pat.sort_indices()
     rp, ci = pat.indptr.astype(np.int32), pat.indices.astype(np.int32)
     info = _lib.BandInfo()
-    rc = _lib.load().fpsq_band_analyze_bordered_cols(n, m, rp.ctypes.data, ci.ctypes.data, int(border), int(cols), None, None,
-                                                     C.byref(info))
+    rc = getattr(_lib.load(), entry)(n, m, rp.ctypes.data, ci.ctypes.data, int(border), int(cols), None, None, C.byref(info))
     return None if rc != 0 else info.as_dict()
 
 

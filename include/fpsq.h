@@ -396,8 +396,9 @@ int fpsq_dense_get_info(fpsq_dense d, fpsq_dense_info *info);
  *     M = A A' + delta I = B + U U',   B = A_b A_b' + delta I (the band that is factored),
  *     M^-1 r = y - Z w,   y = B^-1 r (the sweeps),   Z = B^-1 U,   S = I + U'Z (s x s, S >= I),   w = S^-1 (U'y).
  * A factorisation also forms U ([m][16] in the stored row order), Z (one tile of the block sweeps) and the Cholesky of S;
- * every M-solve of every entry below takes the correction behind its sweeps (two launches more).  SCOPE: a handle takes ONE
- * kind of border, max_border > 0 together with max_cols > 0 is FPSQ_ERR_ARG; at most 16 columns.
+ * every M-solve of every entry below takes the correction behind its sweeps (two launches more).  SCOPE: through THESE entries
+ * (and the older ones above) a handle takes ONE kind of border, max_border > 0 together with max_cols > 0 is FPSQ_ERR_ARG --
+ * both kinds on one handle are the ARROW BAND entries below; at most 16 columns.
  * SELECTION, deterministic, the row border's rule transposed: the candidates are the max_cols columns with the most entries
  * (ties: the lower column index first), taken most first; the long columns are the SHORTEST such prefix after whose removal
  * (a) no row of A is left without an entry (B would be structurally singular at delta = 0) and (b) the remaining columns,
@@ -416,7 +417,39 @@ int fpsq_dense_get_info(fpsq_dense d, fpsq_dense_info *info);
  * on the shapes of the tests where the Cholesky of M gives 1e-15 .. 7e-15; 1e-10 against 1.4e-13 on aug2dc_like(51), delta =
  * 0, with 4 all-row columns scaled by 30, cond(B) = 1e3, cond(M) = 2e5, cond(S) = 9e3).  That loss belongs to the scheme;
  * border_pivot_ratio reports it per factorisation.  A pivot of S that fails the rule of the pivots of B (S >= I, so only behind a
- * failing pivot of B, which keeps *info) is regularised or reported as the last stored row; regularized_pivots counts it. */
+ * failing pivot of B, which keeps *info) is regularised or reported as the last stored row; regularized_pivots counts it.
+ *
+ * ARROW BAND (fpsq_band_create_arrow, _create_coo_arrow, _analyze_arrow: the arguments of the _bordered_cols entries, both
+ * maxima 0 .. 16 INDEPENDENTLY, anything else FPSQ_ERR_ARG).  Border rows and long columns on one handle: a model with a free
+ * final time or a global parameter (a long column) and an integral, mean-value or mass constraint (a long row).  Stored row
+ * order: the mb band rows, then the s_r border rows; columns are not renumbered; L = the s_c long columns, "o" = restricted to
+ * the other columns:
+ *     A = [A_b,o U_b; A_s,o U_s],   M = A A' + delta I = M_r + U U',   U = [U_b; U_s] (m x s_c, ALL rows, the border's included),
+ *     M_r = [B C; C' D],   B = A_b,o A_b,o' + delta I,   C = A_b,o A_s,o',   D = A_s,o A_s,o' + delta I.
+ * M_r^-1 is the bordered band's solve (sweeps on B, w_r = S_r^-1 (t - C'y), u = y - Z_r w_r, Z_r = B^-1 C, S_r = D - C'Z_r) and
+ * the long columns' correction is wrapped around it: M^-1 r = y - Z_c w_c, y = M_r^-1 r, Z_c = M_r^-1 U, S_c = I + U'Z_c >= I,
+ * w_c = S_c^-1 U'y.  A factorisation forms C, D, Z_r, S_r as a bordered handle does (on the other columns), then U, Z_c (the
+ * block sweeps followed by the rows' correction), S_c and G = U_s' - U_b'Z_r (s_c x s_r).  COST of an M-solve behind the
+ * sweeps: FOUR launches in the nested form (the two corrections one after the other); the default FUSED form takes TWO: since
+ * U'M_r^-1 r = U_b'y + G w_r with y the sweeps' output, one reduction forms the partials of C'y and U_b'y in one pass over y
+ * and one update solves with S_r, then S_c, and corrects every row once (u = y - Z_r w_r - Z_c,b w_c on the band rows, w_r -
+ * Z_c,s w_c on the border rows).  FPSQ_ARROW_FUSED=0 (read at create) selects the nested form; the two agree to rounding, not
+ * bitwise.  Everything else is as on the two kinds alone: the border rows' right-hand sides travel in the last stored rows,
+ * the long columns' rows of A'q in the slots behind the padded rows, all sums in a fixed order (DETERMINISM as below).
+ * last_border_ms spans both shares, border_pivot_ratio is S_c's; a failing pivot of S_r follows the row border's rule (*info =
+ * that border row), one of S_c the long columns'; regularized_pivots counts both.
+ * SELECTION, deterministic:  (1) the column candidates Cc are the max_cols columns with the most entries (ties: the lower
+ * index), the row candidates Rc the max_border rows of widest column span measured over the columns NOT in Cc, widest first
+ * (ties: the lower index) -- otherwise a parameter column at the end of the column order makes every row look wide.  (2)
+ * COLUMNS: the rule of LONG COLUMNS (the shortest prefix of Cc meeting (a) and (b)) on the pattern with the rows Rc set aside,
+ * in the baseline ordering and in the trial orderings alike; (a) is checked over ALL rows.  That is L.  (3) ROWS: the rule of
+ * BORDERED BAND on the pattern with the columns L masked: spans, candidates and orderings use the remaining columns, the
+ * quarter is measured against the ordering of all rows on the remaining columns.  That is R.  (4) REDUCTIONS, bit for bit: L
+ * empty -> what the _bordered entries give with max_border; R empty -> the columns are decided again by the plain column rule
+ * and the result is what _bordered_cols(0, max_cols) gives; max_border = 0 resp. max_cols = 0 -> the corresponding older
+ * entry; both empty -> the plain handle.  Each phase costs at most one ordering per candidate prefix.  row_perm lists the
+ * border rows last (ascending), long_cols is as in _analyze_bordered_cols; nblocks, bandwidth_blocks, factor_bytes and
+ * chains describe B. */
 typedef struct fpsq_band_s *fpsq_band;
 typedef struct {
   int64_t n, m, nnz;
@@ -429,8 +462,8 @@ typedef struct {
                                 order of the two elimination chains) */
   int64_t chains;            /* 2: the band is eliminated from both ends at once (two streams), 1: one chain */
   int64_t border_rows;       /* rows eliminated last as a border (0 unless created with max_border > 0 and rows were taken) */
-  double last_border_ms;     /* device time of C, D, Z, S (long columns: U, Z, S) and its Cholesky in the last factorisation
-                                (not in last_chol_ms) */
+  double last_border_ms;     /* device time of C, D, Z, S (long columns: U, Z, S; arrow: both) and its Cholesky in the last
+                                factorisation (not in last_chol_ms) */
   int64_t border_cols;       /* long columns taken out of the band (0 unless created with max_cols > 0 and columns were taken) */
   double border_pivot_ratio; /* long columns: (largest / smallest pivot of the Cholesky factor of S)^2 in the last
                                 factorisation, an estimate of cond(S); 1 without long columns */
@@ -451,6 +484,10 @@ int fpsq_band_create_bordered_cols(fpsq_band *out, int64_t n, int64_t m, const i
 int fpsq_band_create_coo_bordered_cols(fpsq_band *out, int64_t n, int64_t m, int64_t nnz, const int64_t *rows,
                                        const int64_t *cols, int32_t index_base, int32_t max_border, int32_t max_cols,
                                        int32_t device);
+int fpsq_band_create_arrow(fpsq_band *out, int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind,
+                           int32_t max_border, int32_t max_cols, int32_t device);
+int fpsq_band_create_coo_arrow(fpsq_band *out, int64_t n, int64_t m, int64_t nnz, const int64_t *rows, const int64_t *cols,
+                               int32_t index_base, int32_t max_border, int32_t max_cols, int32_t device);
 int fpsq_band_factorize_coo(fpsq_band b, const double *vals, double delta, int32_t *info);
 /* the ordering decisions of fpsq_band_create alone, on the host (no device needed; rowptr / colind in HOST memory): row_perm
  * (m entries, may be null) = the caller's row stored at each position, info = blocks / half bandwidth / factor bytes /
@@ -462,6 +499,8 @@ int fpsq_band_analyze_bordered(int64_t n, int64_t m, const int32_t *rowptr, cons
 /* long_cols (16 entries, may be null): the columns taken, ascending, -1 beyond border_cols */
 int fpsq_band_analyze_bordered_cols(int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind, int32_t max_border,
                                     int32_t max_cols, int32_t *row_perm, int32_t *long_cols, fpsq_band_info *info);
+int fpsq_band_analyze_arrow(int64_t n, int64_t m, const int32_t *rowptr, const int32_t *colind, int32_t max_border,
+                            int32_t max_cols, int32_t *row_perm, int32_t *long_cols, fpsq_band_info *info);
 int fpsq_band_destroy(fpsq_band b);
 const char *fpsq_band_last_error(fpsq_band b);
 int fpsq_band_set_regularization(fpsq_band b, double tol, double reg);
