@@ -135,10 +135,12 @@ __device__ __forceinline__ void lsqr_begin2_step(LsqrState* S, double aa, Progre
   const double Anorm = alpha, rNorm = beta1;
   const bool solved = (ArNorm / (Anorm * rNorm) <= S->axtol) | (1.0 + ArNorm / (Anorm * rNorm) <= 1.0);
   const bool tired = 0 >= S->itmax;
+  // lsqr! tests zero_resid at start-up too (rNorm / beta1 = 1 there) and ranks it over solved, as in the loop
+  const bool zero_resid = (rNorm / beta1 <= S->axtol) | (1.0 + rNorm / beta1 <= 1.0);
   if (solved | tired) {
     S->stats.solved = solved;
-    S->stats.inconsistent = 1;
-    S->stats.status = solved ? FPSQ_ST_SOLVED : FPSQ_ST_MAXITER;
+    S->stats.inconsistent = !zero_resid;
+    S->stats.status = zero_resid ? FPSQ_ST_ZERO_RESID : solved ? FPSQ_ST_SOLVED : FPSQ_ST_MAXITER;
     S->ctl.done = 1;
     publish(prog, 0, 1);
     return;
@@ -493,9 +495,12 @@ __device__ __forceinline__ void lnlq_sa_step(LnlqState* S, double aa, int it, Pr
   sym_givens(S->epsbar, bhat_n, c_n, s_n, eps_k);
   const double eta_n = ahat_n * s_n;
   const double epsbar_n = -ahat_n * c_n;
-  const double tau_n = -bhat_n * S->tau / ahat_n;
+  // Exact breakdown (beta_{k+1} = 0, hence alpha_{k+1} = 0: A = 2 [I 0] gets there in one pass): there is no v_{k+1} and no
+  // wbar_{k+1}, their coefficients are zero -- taken literally the recurrence forms 0 / 0 and the transfer to the CRAIG point
+  // writes NaN over the y of a solved system (the restatement's rule, oracle/fps_oracle.c fpo_lnlq_op)
+  const double tau_n = (ahat_n != 0.0) ? -bhat_n * S->tau / ahat_n : 0.0;
   const double zeta_k = c_n * S->zetabar;
-  const double zetabar_n = (tau_n - eta_n * zeta_k) / epsbar_n;
+  const double zetabar_n = (epsbar_n != 0.0) ? (tau_n - eta_n * zeta_k) / epsbar_n : 0.0;
   double rNorm_lq = S->bNorm;
   if (k != 1) {
     const double t1 = S->epsbar * S->zetabar, t2 = bhat_n * S->sk * S->zeta_km1;
@@ -610,10 +615,13 @@ __device__ __forceinline__ void minres_begin_step(MinresState* S, double bb, Pro
   const double eps_tol = S->atol + S->rtol * beta1;
   const bool solved = beta1 <= S->rtol;
   const bool tired = 0 >= S->itmax;
+  // minres! ranks zero_resid over solved at start-up as in the loop; solved alone (beta1 <= rtol with atol + rtol beta1 < beta1,
+  // e.g. beta1 = 0.5, rtol = 0.7) stays SOLVED with inconsistent = 1
+  const bool zero_resid = beta1 <= eps_tol;
   if (solved | tired) {
     S->stats.solved = solved;
-    S->stats.inconsistent = !(beta1 <= eps_tol);
-    S->stats.status = solved ? FPSQ_ST_SOLVED : FPSQ_ST_MAXITER;
+    S->stats.inconsistent = !zero_resid;
+    S->stats.status = zero_resid ? FPSQ_ST_ZERO_RESID : solved ? FPSQ_ST_SOLVED : FPSQ_ST_MAXITER;
     S->ctl.done = 1;
     S->ctlT.done = 1;
     publish(prog, 0, 1);

@@ -40,7 +40,7 @@ class _Handle:
     def two(self, fn, r1, r2, sizes):
         r1 = np.ascontiguousarray(r1, dtype=np.float64)
         r2 = np.ascontiguousarray(r2, dtype=np.float64)
-        outs = [np.empty(k) for k in sizes]
+        outs = [np.full(k, np.nan) for k in sizes]   # (preset: an output the call leaves untouched shows)
         rc = fn(self.h, r1.ctypes.data, r2.ctypes.data, *[o.ctypes.data for o in outs], self.st)
         assert rc >= 0, self.err()
         return (*outs, rc)
@@ -53,6 +53,24 @@ class _Handle:
 
     def solve_two_extras(self, r1, r2):
         return self.two(self.lib.fpsq_solve_two_extras, r1, r2, (self.m, self.m))
+
+    def ys_gs(self, g, c, sigma):
+        """fpsq_ys_gs -> (gs, ys, v, w, rc)"""
+        fn = self.lib.fpsq_ys_gs
+        return self.two(lambda h, a, b, *rest: fn(h, a, b, sigma, *rest), g, c, (self.n, self.m, self.n, self.m))
+
+    def expect(self, iterations):
+        """The run-ahead count of the NEXT solve call only (fpsq_debug_expect_iterations)."""
+        assert self.lib.fpsq_debug_expect_iterations(self.h, iterations) == 0, self.err()
+
+    def stats(self):
+        """(niter, status, solved, rnorm, arnorm, inconsistent) of the two systems of the last call: lane_cases.restate(full=True)"""
+        return [(s.niter, s.status, s.solved, s.rnorm, s.arnorm, s.inconsistent) for s in self.st]
+
+    def counters(self):
+        i = _lib.Info()
+        assert self.lib.fpsq_get_info(self.h, C.byref(i)) == 0
+        return (i.fuse_fallbacks, i.wait_timeouts, i.p2p_timeouts)
 
     def close(self):
         self.lib.fpsq_destroy(self.h)

@@ -54,21 +54,27 @@ def cut_options(lane, k):
     return dict(ne_itmax=k)   # minres-k (the device handle adds kkt_method = 1)
 
 
-def _stats(st):
-    return (st.niter, st.status, st.solved, st.rnorm, st.arnorm)
+def _stats(st, full=False):
+    """full: `inconsistent` appended -- compare() holds whatever follows arnorm to equality (tests/stopping_cases.py)."""
+    return (st.niter, st.status, st.solved, st.rnorm, st.arnorm) + ((st.inconsistent,) if full else ())
 
 
-def restate(oracle, lane, ins, delta, opts, csr=None):
+def restate(oracle, lane, ins, delta, opts, csr=None, full=False):
     """The lane's calls by the C restatement in its current summation order.  opts: cut_options(...) or TIGHT (+ ln_method);
-    csr: another matrix of the same shape (the corrupted references of the CPU test)."""
+    csr: another matrix of the same shape (the corrupted references of the CPU test).  lane "lnlq" is solve_two_mixed(g, c) with
+    whatever least-norm method opts name ("mixed" is its other name), "lsq" is solve_two_least_squares(g, r1) on the LSQR
+    lanes; full: the statistics carry `inconsistent` too."""
     m, n = ins["m"], ins["n"]
     rp, ci, va = csr or ins["csr"]
-    if lane == "lnlq":
+    if lane in ("lnlq", "mixed"):
         o = oracle.solve_two_mixed(m, n, rp, ci, va, delta, ins["g"], ins["c"], opts=oracle.default_options(n, m, **opts))
-        return [(o[5], [_stats(s) for s in o[4]], list(o[:4]))]
+        return [(o[5], [_stats(s, full) for s in o[4]], list(o[:4]))]
+    if lane == "lsq":
+        o = oracle.solve_two_least_squares(m, n, rp, ci, va, delta, ins["g"], ins["r1"], opts=oracle.default_options(n, m, **opts))
+        return [(o[5], [_stats(s, full) for s in o[4]], list(o[:4]))]
     if lane == "extras":
         o = oracle.solve_two_extras(m, n, rp, ci, va, delta, ins["r1"], ins["r2"], opts=oracle.default_options(n, m, **opts))
-        return [(o[3], [_stats(s) for s in o[2]], list(o[:2]))]
+        return [(o[3], [_stats(s, full) for s in o[2]], list(o[:2]))]
     kw = dict(itmax=opts.get("ne_itmax", 0))
     for name in ("atol", "rtol", "etol", "conlim"):
         if "ne_" + name in opts:
@@ -77,7 +83,7 @@ def restate(oracle, lane, ins, delta, opts, csr=None):
     calls = []
     for a, b in ((w[0], w[1]), (w[0], w[2])):   # solve_two_mixed(g, c), solve_two_least_squares(g, r1)
         rc = (0 if a[2].solved else 1) | (0 if b[2].solved else 2)   # (the rule of every two-system entry: fps_oracle.c)
-        calls.append((rc, [_stats(a[2]), _stats(b[2])], [a[0], a[1], b[0], b[1]]))
+        calls.append((rc, [_stats(a[2], full), _stats(b[2], full)], [a[0], a[1], b[0], b[1]]))
     return calls
 
 
@@ -109,13 +115,16 @@ def is_finite(calls):
     return all(np.all(np.isfinite(v)) for c in calls for v in c[2])
 
 
-def spread(oracle, lane, kind, delta, k):
-    """How far re-association alone moves the lane's vectors at this cut: orders 1 and 2 against order 0.  (Python's max() passes
-    a NaN over, hence the assertion: a run that broke down measures no rounding.)"""
-    want = cut_reference(oracle, lane, kind, delta, k)
-    alts = [cut_reference(oracle, lane, kind, delta, k, order) for order in (1, 2)]
+def spread_of(want, alts):
+    """How far re-association alone moves the vectors of a result: the other summation orders against order 0.  (Python's max()
+    passes a NaN over, hence the assertion: a run that broke down measures no rounding.)"""
     assert is_finite(want) and all(is_finite(alt) for alt in alts)
     return max(vector_distance(alt, want) for alt in alts)
+
+
+def spread(oracle, lane, kind, delta, k):
+    """spread_of() at this cut: orders 1 and 2 against order 0."""
+    return spread_of(cut_reference(oracle, lane, kind, delta, k), [cut_reference(oracle, lane, kind, delta, k, order) for order in (1, 2)])
 
 
 def allowance(spread_, k):
@@ -125,16 +134,17 @@ def allowance(spread_, k):
 
 
 def compare(got, want, tol, what=""):
-    """The assertion of the fixed cuts: equal return codes, equal (niter, status, solved) per lane, the residual estimates within
-    tol * max(|want|, 1), every vector within tol in relative inf-norm.  All failures of a comparison are reported together."""
+    """The assertion of the fixed cuts: equal return codes, equal (niter, status, solved) per lane -- and equal `inconsistent` where
+    the statistics carry it behind arnorm (restate(full=True)) --, the residual estimates within tol * max(|want|, 1), every vector
+    within tol in relative inf-norm.  All failures of a comparison are reported together."""
     bad = []
     assert len(got) == len(want)
     for ic, ((rc_g, st_g, v_g), (rc_w, st_w, v_w)) in enumerate(zip(got, want)):
         if rc_g != rc_w:
             bad.append(f"call {ic}: return code {rc_g} != {rc_w}")
         for i, (sg, sw) in enumerate(zip(st_g, st_w)):
-            if tuple(sg[:3]) != tuple(sw[:3]):
-                bad.append(f"call {ic} lane {i}: (niter, status, solved) {tuple(sg[:3])} != {tuple(sw[:3])}")
+            if tuple(sg[:3]) + tuple(sg[5:]) != tuple(sw[:3]) + tuple(sw[5:]):
+                bad.append(f"call {ic} lane {i}: (niter, status, solved) {tuple(sg[:3]) + tuple(sg[5:])} != {tuple(sw[:3]) + tuple(sw[5:])}")
             for j, name in ((3, "rnorm"), (4, "arnorm")):
                 if not abs(sg[j] - sw[j]) <= tol * max(abs(sw[j]), 1.0):
                     bad.append(f"call {ic} lane {i}: estimate {name} {sg[j]!r} != {sw[j]!r}")
