@@ -144,6 +144,12 @@ SYMBOLS = [
     ("fpsq_band_qp_hprod", C.c_int, [_VP, _VP, _DP, _D, _D, _D, _I32, _DP]),
     ("fpsq_band_jac_mul", C.c_int, [_VP, _I32, _D, _DP, _D, _DP]),
     ("fpsq_band_set_input_stream", C.c_int, [_VP, _I32, _VP]),
+    ("fpsq_band_nlp_create", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.POINTER(_VP)]),
+    ("fpsq_band_nlp_destroy", C.c_int, [_VP]),
+    ("fpsq_band_nlp_objgrad", C.c_int, [_VP, _VP, _DP, _D, _D, _D, _D, _DP, C.POINTER(C.c_double), _DP, _DP, _DP,
+                                        C.POINTER(C.c_int32)]),
+    ("fpsq_band_nlp_hprod", C.c_int, [_VP, _VP, _DP, _D, _D, _D, _I32, _DP]),
+    ("fpsq_band_nlp_cons", C.c_int, [_VP, _VP, _DP, _DP]),
     ("fpsq_band_solve_two_least_squares_block", C.c_int, [_VP, _I32, _DP, _DP, _DP, _DP, _DP, _DP]),
     ("fpsq_band_qp_hprod_block", C.c_int, [_VP, _VP, _I32, _DP, _D, _D, _D, _I32, _DP]),
     ("fpsq_band_qp_objgrad_block", C.c_int, [_VP, _VP, _I32, _DP, _DP, _DP, _D, _D, _D, _DP, _DP, _DP, _DP, _DP]),

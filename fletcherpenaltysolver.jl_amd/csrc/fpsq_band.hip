@@ -1,6 +1,6 @@
 // fpsq_band.hip -- host side of the banded direct back-end (C ABI: include/fpsq.h, "band" section): the symbolic phase
 // (ordering, two elimination chains), the block-banded factorisation and the solves, the device-resident eq-QP model
-// (fpsq_band_qp_*) and the block entries.
+// (fpsq_band_qp_*), the model with nonlinear constraints (fpsq_band_nlp_*: fpsq_band_nlp.hip.h) and the block entries.
 #include "fpsq_band.hip.h"
 #include "fpsq_qcsr.h"
 
@@ -71,6 +71,9 @@ struct fpsq_band_s : DirectCore {
   int bc_grid = 1;
   int32_t* lc_cols = nullptr;
   bool arrow_fused = true;
+  // counts the numeric factorisations of this handle, whoever asked for them: a model that depends on the values a
+  // factorisation left in vals / t_vals (fpsq_band_nlp_*) remembers the count it saw
+  uint64_t fact_gen = 0;
   fpsq_band_info info{};
 };
 
@@ -1060,6 +1063,7 @@ int band_create(fpsq_band* out, int64_t n, int64_t m, const int32_t* rowptr, con
                 int32_t max_cols, bool arrow, int32_t device);
 int band_create_coo(fpsq_band* out, int64_t n, int64_t m, int64_t nnz, const int64_t* rows, const int64_t* cols,
                     int32_t index_base, int32_t max_border, int32_t max_cols, bool arrow, int32_t device);
+int band_factor_numeric(fpsq_band b, double delta, int32_t* info);
 }  // namespace
 
 extern "C" {
@@ -1382,7 +1386,6 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
   if (!b || (!vals && b->nnz > 0) || !(delta >= 0.0)) return FPSQ_ERR_ARG;
   hipSetDevice(b->device);
   hipStream_t s = b->stream;
-  const int nb = (int)b->nb, W = b->band_w, bw = W - 1;
   b->factored = false;
   if (int rc = wait_input(b)) return rc;  // (device-resident values produced on a stream registered with fpsq_band_set_input_stream)
   b->have_vals = true;
@@ -1400,6 +1403,18 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
       hipLaunchKernelGGL(k_gather_d, dim3((unsigned)std::min<int64_t>((b->fb_nnz + 255) / 256, 4096)), dim3(256), 0, s, b->vals,
                          b->fb_perm, b->fb_vals, b->fb_nnz);
   }
+  return band_factor_numeric(b, delta, info);
+}
+}  // extern "C"
+
+namespace {
+// The numeric phase of a factorisation on the values that lie in vals / t_vals [/ fb_vals] (fpsq_band_factorize uploads them,
+// fpsq_band_nlp_objgrad writes them in place): form, Cholesky, factor_end.  Synchronous; the return value and *info are
+// fpsq_band_factorize's.
+int band_factor_numeric(fpsq_band b, double delta, int32_t* info) {
+  hipStream_t s = b->stream;
+  const int nb = (int)b->nb, W = b->band_w, bw = W - 1;
+  ++b->fact_gen;
   CHK(b, hipMemsetAsync(b->info_dev, 0, 8, s));
   CHK(b, hipMemsetAsync(b->Mb, 0, (size_t)nb * W * kDB * kDB * 8, s));
   hipEventRecord(b->e0, s);
@@ -1470,6 +1485,9 @@ int fpsq_band_factorize(fpsq_band b, const double* vals, double delta, int32_t* 
     *info = pivot > 0 && b->reordered && pivot <= (int32_t)b->m ? b->rperm_host[pivot - 1] + 1 : pivot;
   return rc;
 }
+}  // namespace
+
+extern "C" {
 
 int fpsq_band_solve_two_mixed(fpsq_band b, const double* rhs1, const double* rhs2, double* p1, double* q1, double* p2,
                               double* q2) {
@@ -1558,7 +1576,8 @@ void bq_launches(fpsq_band b, fpsq_band_qp qp, bool hp, const double* x, const d
 // source are filled from it.  False: a call failed.
 struct QpBuf { void** p; size_t bytes; const void* src; hipMemcpyKind kind; };
 
-bool qp_buffers(fpsq_band_qp qp, std::initializer_list<QpBuf> bufs) {
+template <class Model>
+bool qp_buffers(Model* qp, std::initializer_list<QpBuf> bufs) {
   for (const QpBuf& u : bufs) {
     if (hipMalloc(u.p, u.bytes) != hipSuccess) return false;
     qp->allocs.push_back(*u.p);
@@ -1742,6 +1761,9 @@ int fpsq_band_jac_mul(fpsq_band b, int32_t trans, double alpha, const double* x,
   return FPSQ_OK;
 }
 }  // extern "C"
+
+// ------------------- nonlinear (separable-quadratic) equality constraints on the banded handle: kernels and fpsq_band_nlp_*
+#include "fpsq_band_nlp.hip.h"
 
 // ------------------------------------------- block entries: a (k, n) block of vectors per call, 8 vectors per pass of the factor
 

@@ -428,6 +428,108 @@ class DeviceArrowBandEqQP(DeviceBandEqQP):
         super().__init__(qp, **kwargs)
 
 
+class DeviceBandSepQuadNLP:
+    """The device-resident model with NONLINEAR equality constraints on the banded direct back-end (`fpsq_band_nlp_*`):
+    `nlp_data` is a `problems.SepQuadNLP` (`problems.with_quadratic_constraints`) -- the QP's objective with
+    c_i(x) = sum_j (A_ij + 1/2 H_ij x_j) x_j - b_i.  The Jacobian moves with x, so every `objgrad` writes J(x) into the handle
+    and refactorises J J' + delta I (`info()["factorizations"]` counts them); `hprod` runs at the point of the last objgrad, on
+    its factor, and the two `hessian_approx` modes differ.  `objgrad` / `hprod` have DeviceBandEqQP's parameter lists;
+    `fps_solve_device` takes the object (`nonlinear = True` selects the penalty wrapper that keeps track of that point).
+    `qp` is the underlying EqQP (objective, pattern, x, xhat)."""
+
+    nonlinear = True
+
+    def __init__(self, nlp_data, sigma=1e3, rho=1.0, delta=0.0, eta=0.0, device=0, ldlt_tol=None, ldlt_r2=None):
+        from .qdsolver import _ldlt_r2
+
+        self._lib = _lib.load()
+        qp = nlp_data.qp
+        self.nlp_data, self.qp = nlp_data, qp
+        self.sigma, self.rho, self.delta, self.eta = sigma, rho, float(delta), eta
+        self.device = int(device)
+        self._h = self._q = None
+        self.factorizations = 0
+        self._in_stream = -1
+        rp = np.ascontiguousarray(qp.rowptr, dtype=np.int32)
+        ci = np.ascontiguousarray(qp.colind, dtype=np.int32)
+        h = C.c_void_p()
+        if self._lib.fpsq_band_create(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, self.device) != 0:
+            raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
+        self._h = h
+        try:
+            se = float(np.sqrt(np.finfo(float).eps))
+            self.ldlt_tol = se if ldlt_tol is None else float(ldlt_tol)
+            self.ldlt_r2 = _ldlt_r2(ldlt_r2)
+            self._check(self._lib.fpsq_band_set_regularization(h, self.ldlt_tol, -self.ldlt_r2))
+            f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+            q = C.c_void_p()
+            self._check(self._lib.fpsq_band_nlp_create(h, f64(qp.qdiag).ctypes.data, f64(qp.d).ctypes.data,
+                                                       f64(nlp_data.b).ctypes.data, f64(qp.vals).ctypes.data,
+                                                       f64(nlp_data.hvals).ctypes.data, C.byref(q)))
+            self._q = q
+        except Exception:
+            self.close()
+            raise
+
+    _check = DeviceBandEqQP._check
+    _order = DeviceBandEqQP._order
+
+    def set_delta(self, delta):
+        """The delta of the NEXT objgrad's factorisation (an hprod stays on the factor of the last one)."""
+        self.delta = float(delta)
+
+    def objgrad(self, x, gx=None, ys=None, gs=None, xk=None):
+        """One objgrad at a fresh x, its factorisation included.  Returns (fx, rc); with rc = 1 (J J' + delta I not positive
+        definite and no regularisation) nothing was evaluated: fx is nan and the outputs are untouched."""
+        fx = C.c_double()
+        self._order(x, gx, ys, gs, xk)
+        rc = self._check(self._lib.fpsq_band_nlp_objgrad(self._h, self._q, _lib.ptr(x), self.sigma, self.rho, self.eta,
+                                                         self.delta, _lib.ptr(xk), C.byref(fx), _lib.ptr(gx), _lib.ptr(ys),
+                                                         _lib.ptr(gs), None))
+        self.factorizations += 1
+        if rc:
+            import warnings
+            warnings.warn("DeviceBandSepQuadNLP: J J' + delta I is not positive definite (no valid factorisation)")
+            return float("nan"), rc
+        return fx.value, 0
+
+    def hprod(self, v, Hv, hessian_approx=2):
+        """hprod!(::FletcherPenaltyNLP, x, v, Hv) at the x of the last objgrad (include/fpsq.h fpsq_band_nlp_hprod).  Returns rc."""
+        self._order(v, Hv)
+        return self._check(self._lib.fpsq_band_nlp_hprod(self._h, self._q, _lib.ptr(v), self.sigma, self.rho, self.eta,
+                                                         int(hessian_approx), _lib.ptr(Hv)))
+
+    def cons(self, x, c):
+        """c = c(x), in the caller's row order (no factorisation needed)."""
+        self._order(x, c)
+        return self._check(self._lib.fpsq_band_nlp_cons(self._h, self._q, _lib.ptr(x), _lib.ptr(c)))
+
+    def jac_mul(self, trans, alpha, x, beta, y):
+        """y = alpha op(J) x + beta y with J = the Jacobian at the x of the last objgrad (fpsq_band_jac_mul)."""
+        self._order(x, y)
+        return self._check(self._lib.fpsq_band_jac_mul(self._h, int(trans), float(alpha), _lib.ptr(x), float(beta),
+                                                       _lib.ptr(y)))
+
+    def info(self):
+        i = _lib.BandInfo()
+        self._check(self._lib.fpsq_band_get_info(self._h, C.byref(i)))
+        return {**i.as_dict(), "factorizations": self.factorizations}
+
+    def close(self):
+        if getattr(self, "_q", None):
+            self._lib.fpsq_band_nlp_destroy(self._q)
+            self._q = None
+        if getattr(self, "_h", None):
+            self._lib.fpsq_band_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def rccl_unique_id() -> bytes:
     """128-byte RCCL id (call on rank 0, broadcast, pass to every rank's DeviceEqQP(comm=("rccl", ...)))."""
     lib = _lib.load()

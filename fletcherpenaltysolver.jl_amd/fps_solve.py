@@ -683,6 +683,35 @@ class _DevicePenalty:
         return {"objgrad_calls": self.nobjgrad, "hprod_calls": self.nhprod}
 
 
+class _DeviceNLPPenalty(_DevicePenalty):
+    """The penalty function of a device-resident model with NONLINEAR constraints (DeviceBandSepQuadNLP, fpsq_band_nlp_*): the
+    constraints go through `dev.cons`, and a Hessian product belongs to the point of the handle's last objgrad -- after a
+    rejected trial point that is the trial point, so `hprod_` compares x with a clone of that point and evaluates again when
+    the sub-solver has moved back."""
+
+    def __init__(self, dev, torch, hessian_approx=2):
+        super().__init__(dev, torch, hessian_approx)
+        self._x_at = None   # a clone of the x of the last objgrad
+
+    def objgrad_(self, x, g):
+        fx, g = super().objgrad_(x, g)
+        self._x_at = x.clone()
+        return fx, g
+
+    def hprod_(self, x, v, Hv):
+        if self._x_at is None or not self.torch.equal(x, self._x_at):
+            self.objgrad_(x, self.scratch)
+        return super().hprod_(x, v, Hv)
+
+    def invalidate(self):
+        super().invalidate()
+        self._x_at = None   # (sigma, rho, delta or eta changed: ys, gs and the factor belong to the old parameters)
+
+    def _cons(self, x):
+        self.dev.cons(x, self.c)
+        return self.c
+
+
 def fps_solve_device(dev, x0, *, atol=_SE, rtol=_SE, max_iter=100, max_time=300.0, verbose=0, **kwargs):
     """fps_solve on a device-resident equality QP (`DeviceEqQP` / `DeviceSparseHessianEqQP`: the iterative back-end, with a
     diagonal / a sparse symmetric objective Hessian, or `DeviceBandEqQP`: the banded direct one, `DeviceBorderedBandEqQP` / `DeviceArrowBandEqQP`
@@ -694,4 +723,6 @@ def fps_solve_device(dev, x0, *, atol=_SE, rtol=_SE, max_iter=100, max_time=300.
     meta = AlgoData(**{k: v for k, v in kwargs.items() if k in AlgoData.__dataclass_fields__})
     dev.sigma, dev.rho, dev.eta = meta.sigma_0, meta.rho_0, 0.0
     dev.set_delta(0.0)
-    return _outer_loop(_DevicePenalty(dev, torch, meta.hessian_approx), x0, meta, atol, rtol, max_iter, max_time, verbose)
+    # a model with nonlinear constraints (DeviceBandSepQuadNLP: fpsq_band_nlp_*) says so itself
+    penalty = _DeviceNLPPenalty if getattr(dev, "nonlinear", False) else _DevicePenalty
+    return _outer_loop(penalty(dev, torch, meta.hessian_approx), x0, meta, atol, rtol, max_iter, max_time, verbose)

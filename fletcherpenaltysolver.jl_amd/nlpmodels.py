@@ -266,6 +266,43 @@ class EqQPModel(_Model):
         return obj_weight * self.qp.qdiag * np.asarray(v)
 
 
+class SepQuadConModel(EqQPModel):
+    """Host view of problems.SepQuadNLP: the QP's objective with the separable-quadratic equality constraints
+    c_i(x) = sum_j (A_ij + 1/2 H_ij x_j) x_j - b_i = 0 (meta.lcon = 0).  J(x)_ij = A_ij + H_ij x_j has the pattern of A for
+    every x, sum_i y_i Hess c_i = diag(H'y) and ghjvprod(x, g, v) = H (g .* v)."""
+
+    def __init__(self, data):
+        import scipy.sparse as sp
+
+        qp = data.qp
+        assert getattr(qp, "hess_vals", None) is None
+        super().__init__(qp)
+        self.data = data
+        self.hvals = np.ascontiguousarray(data.hvals, dtype=np.float64)
+        self.b = np.ascontiguousarray(data.b, dtype=np.float64)
+        self._H = sp.csr_matrix((self.hvals, qp.colind, qp.rowptr), shape=(qp.m, qp.n))
+        self.meta.lcon = np.zeros(qp.m)
+        self.meta.name = qp.name + "-sepquad"
+
+    def _J(self, x):
+        import scipy.sparse as sp
+
+        return sp.csr_matrix((self.jac_coord(x), self.qp.colind, self.qp.rowptr), shape=(self.qp.m, self.qp.n))
+
+    def cons(self, x):
+        x = np.asarray(x, float)
+        return self._A @ x + 0.5 * (self._H @ (x * x)) - self.b
+
+    def jac_coord(self, x): return self.qp.vals + self.hvals * np.asarray(x, float)[self.qp.colind]
+    def jprod(self, x, v): return self._J(x) @ v
+    def jtprod(self, x, v): return self._J(x).T @ v
+
+    def hprod(self, x, y, v, obj_weight=1.0):
+        return obj_weight * self.qp.qdiag * np.asarray(v) + (self._H.T @ y) * np.asarray(v)
+
+    def ghjvprod(self, x, g, v): return self._H @ (np.asarray(g) * np.asarray(v))
+
+
 class TorchEqQPModel(EqQPModel):
     """The same model with its Jacobian RESIDENT ON THE GPU (torch): `jac_coord` returns a device tensor, which the direct
     back-ends take in place (fpsq_dense_set_jacobian_coo / fpsq_band_factorize_coo: no Jacobian value crosses PCIe), and

@@ -205,6 +205,32 @@ def with_arrow(qp: EqQP, s_rows: int, s_cols: int, row_kind: str = "mean", col_k
     return with_long_columns(with_border_rows(qp, s_rows, kind=row_kind, seed=seed), s_cols, kind=col_kind, seed=seed)
 
 
+@dataclass
+class SepQuadNLP:
+    """A QP objective with separable-quadratic equality constraints on the pattern of the QP's Jacobian:
+    c_i(x) = sum_j (A_ij + 1/2 H_ij x_j) x_j - b_i, so J(x)_ij = A_ij + H_ij x_j (nlpmodels.SepQuadConModel,
+    include/fpsq.h fpsq_band_nlp_*).  `qp` holds the objective, A (rowptr / colind / vals), x and xhat; its own b is that of
+    the LINEAR constraints and is not used."""
+
+    qp: EqQP
+    hvals: np.ndarray  # H in the CSR order of qp.vals
+    b: np.ndarray      # right-hand side, c(xhat) = 0
+
+
+def with_quadratic_constraints(qp: EqQP, curv: float = 0.1, seed: int = 0) -> SepQuadNLP:
+    """`qp` with curvature in every constraint: hvals = curv * vals * U(0.5, 1.5) * (+-1) (numpy's default_rng(seed), one draw
+    of each per entry) and b = A xhat + 1/2 H (xhat .* xhat), so that xhat stays feasible.  The QP must have a diagonal
+    Hessian."""
+    import scipy.sparse as sp
+
+    assert qp.hess_vals is None
+    rng = np.random.default_rng(seed)
+    hvals = curv * qp.vals * rng.uniform(0.5, 1.5, qp.vals.size) * rng.choice([-1.0, 1.0], qp.vals.size)
+    H = sp.csr_matrix((hvals, qp.colind, qp.rowptr), shape=(qp.m, qp.n))
+    b = qp.scipy_csr() @ qp.xhat + 0.5 * (H @ (qp.xhat * qp.xhat))
+    return SepQuadNLP(qp, np.ascontiguousarray(hvals, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64))
+
+
 def _stratified_rows(m, n, per_row, start, width, seed, diag_col=None, diag_boost=0.0):
     """Each of the m rows gets `per_row` sorted, distinct columns: one per stratum of
     [start[i], start[i] + width).  If diag_col is given, the stratum containing diag_col[i] is

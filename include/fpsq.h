@@ -561,6 +561,57 @@ int fpsq_band_qp_hprod(fpsq_band b, fpsq_band_qp qp, const double *v, double sig
 int fpsq_band_jac_mul(fpsq_band b, int32_t trans, double alpha, const double *x, double beta, double *y);
 int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
 
+/* ---- the device-resident model with NONLINEAR equality constraints on the banded handle: a QP objective with
+ * separable-quadratic constraints on the pattern of A,
+ *     f(x) = 1/2 x' diag(q) x + d'x,    c_i(x) = sum_j (A_ij + 1/2 H_ij x_j) x_j - b_i,    H has exactly the sparsity of A,
+ * so that J(x)_ij = A_ij + H_ij x_j keeps the handle's pattern for every x, sum_i y_i Hess c_i = diag(H'y) and
+ * ghjvprod(x, g, v) = H (g .* v).  Unlike the fpsq_band_qp_* group, whose Jacobian is constant and whose factor is the caller's
+ * to keep, this model's Jacobian moves with x: an objgrad REFACTORISES, as the reference's LDLtSolver does per solve_two_mixed
+ * (src/solve_linear_system.jl:223-251).  The multiplier-weighted curvature in Hsv, Sstw, ghjvprod and the separate hprod! Val(1)
+ * (src/model-Fletcherpenaltynlp.jl:382-399, :572-634), which vanish on the fpsq_band_qp_* model, are live here.  Pointers are
+ * host or device pointers, calls are synchronous and honour fpsq_band_set_input_stream; sums are formed in a fixed order (same
+ * arguments, same bits).
+ *   fpsq_band_nlp_create  a_vals, h_vals: the values of A and H in the order fpsq_band_factorize takes its values (the CSR the
+ *                         handle was created with); bvec in the caller's row order.  All are copied.  Handles without border rows
+ *                         or long columns are accepted, reordered and two-chain ones included; a handle with border rows, with
+ *                         long columns (they change the transposed structure) or created by a fpsq_band_create_coo* entry (its
+ *                         callers do not know the slot order) gives FPSQ_ERR_STATE and a message that names which.
+ *   fpsq_band_nlp_objgrad one `objgrad!` at a fresh x: (1) J(x) is written into the handle's value arrays; (2) the numeric
+ *                         factorisation of J J' + delta I runs on them -- the return value is the soft code 1 with *info (may be
+ *                         NULL) as fpsq_band_factorize gives them, and with it nothing is evaluated and no output is written;
+ *                         (3) (p1, q1, p2, q2) = solve_two_mixed(g, c), g = q .* x + d; (4) ys = q1 + sigma q2,
+ *                         gs = p1 + sigma p2,
+ *                           gx = gs - (q - H'ys) .* p2 + sigma p2 + (H'q2) .* gs + rho J'c + eta (x - xk);
+ *                         (5) *fx = f - c'ys + rho/2 c'c + eta/2 |x - xk|^2 (a HOST double).  The rho and eta terms enter only
+ *                         when the parameter is positive; xk NULL means 0; gx, ys, gs may be NULL.  gx is the gradient of the
+ *                         function *fx is a value of: Hsv is formed with -ys, as `hprod!` and `hess_coord!` form it (:477, :538,
+ *                         :590), not with +ys as `grad!` has it (:382, :415) -- the two agree only when the constraints are
+ *                         linear.  AFTERWARDS THE HANDLE'S VALUES ARE J(x): fpsq_band_jac_mul multiplies with J(x), and
+ *                         a fpsq_band_qp_* model on this handle would evaluate on J(x) until the handle is factorised again.
+ *   fpsq_band_nlp_hprod   one `hprod!` at the point of the LAST SUCCESSFUL objgrad of this model, on its factor.  The model
+ *                         keeps qe = q - H'ys, hc = H'c and gs from that evaluation.
+ *                         hessian_approx = 2 (:521-570): (p1, _, p2, _) = solve_two_least_squares(v, qe .* v), Ptv = v - p1,
+ *                           Hv = p2 - qe .* Ptv + 2 sigma Ptv [+ hc .* v + rho J'(J v)] [+ eta v]
+ *                         (the brackets enter when rho > 0 resp. eta > 0; Hcv is NOT scaled by rho, :562).
+ *                         hessian_approx = 1 (:572-634): the same with rho (hc .* v + J'(J v)) (:626), and additionally
+ *                           Hv -= J'z + (H'q1) .* gs,   z = M^-1 H (gs .* v),  q1 = M^-1 J v (the first solve's own multipliers).
+ *                         z comes from the cached factor, M = J J' + delta I: the reference's tau = max(delta, 1e-14) (:148 of
+ *                         solve_linear_system.jl) differs only for delta < 1e-14, by O(1e-14 |M^-1|).  Any other value:
+ *                         FPSQ_ERR_ARG.  Without a prior successful objgrad of THIS model, or when anyone has factorised the
+ *                         handle since (fpsq_band_factorize[_coo], another model's objgrad): FPSQ_ERR_STATE with a message -- the
+ *                         handle counts its factorisations and the model remembers the count it saw.
+ *   fpsq_band_nlp_cons    c(x) in the caller's row order: one launch on the model's own arrays, no factor needed.
+ * Destroy a model before the handle it was created on. */
+typedef struct fpsq_band_nlp_s *fpsq_band_nlp;
+int fpsq_band_nlp_create(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
+                         const double *h_vals, fpsq_band_nlp *out);
+int fpsq_band_nlp_destroy(fpsq_band_nlp nlp);
+int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double *x, double sigma, double rho, double eta, double delta,
+                          const double *xk, double *fx, double *gx, double *ys, double *gs, int32_t *info);
+int fpsq_band_nlp_hprod(fpsq_band b, fpsq_band_nlp nlp, const double *v, double sigma, double rho, double eta,
+                        int32_t hessian_approx, double *Hv);
+int fpsq_band_nlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double *x, double *c);
+
 /* ---- block entries on the cached banded factor: k vectors per call.  A triangular sweep streams the whole factor whether it
  * carries one vector or several, so these entries carry a TILE of 8 vectors (16 right-hand-side columns: the two M-solves of
  * each) through one pair of sweeps on the fp64 matrix cores; k > 8 is processed in successive tiles of 8.
