@@ -145,6 +145,7 @@ SYMBOLS = [
     ("fpsq_band_jac_mul", C.c_int, [_VP, _I32, _D, _DP, _D, _DP]),
     ("fpsq_band_set_input_stream", C.c_int, [_VP, _I32, _VP]),
     ("fpsq_band_nlp_create", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.POINTER(_VP)]),
+    ("fpsq_band_nlp_create_arrow", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.POINTER(_VP)]),
     ("fpsq_band_nlp_destroy", C.c_int, [_VP]),
     ("fpsq_band_nlp_objgrad", C.c_int, [_VP, _VP, _DP, _D, _D, _D, _D, _DP, C.POINTER(C.c_double), _DP, _DP, _DP,
                                         C.POINTER(C.c_int32)]),

@@ -64,8 +64,8 @@ struct fpsq_band_s : DirectCore {
   double* fb_vals = nullptr;
   // the long columns' own set, so that a handle can carry both kinds (the rows keep bd_*): bc_c / bc_z: U and Z_c, [mpad][16];
   // bc_l: the factor of S_c; bc_part: [bc_grid][256]; bc_t: [256] unused slots of a reduction, then the pivot ratio; bc_grid:
-  // workgroups of the columns' reductions, over all m rows (vrows = 16 bc_grid).  ARROW (fpsq_band_create_arrow, border > 0 and
-  // cols > 0; fpsq_band.hip.h "arrow band"): lc_cols: the long columns, ascending; bc_g: G = U_s' - U_b'Z_r, [16][16];
+  // workgroups of the columns' reductions, over all m rows (vrows = 16 bc_grid); lc_cols: the long columns, ascending.  ARROW
+  // (fpsq_band_create_arrow, border > 0 and cols > 0; fpsq_band.hip.h "arrow band"): bc_g: G = U_s' - U_b'Z_r, [16][16];
   // behind bc_part's [bc_grid][256] the rows' partials of the fused reduction, [bd_grid][256]; arrow_fused: FPSQ_ARROW_FUSED (default 1)
   double *bc_c = nullptr, *bc_z = nullptr, *bc_l = nullptr, *bc_part = nullptr, *bc_t = nullptr, *bc_g = nullptr;
   int bc_grid = 1;
@@ -948,9 +948,9 @@ int cols_setup(fpsq_band b, const BandSymbolic& sy) {
   int rc = chain16_setup(b) || dalloc(b, &b->bc_c, tile) || dalloc(b, &b->bc_z, tile) ||
            dalloc(b, &b->bc_l, (size_t)kBorderMax * kBorderMax) || dalloc(b, &b->bc_part, parts) ||
            dalloc(b, &b->bc_t, 256 + 8) || dalloc(b, &b->bd_keep, (size_t)(b->mpad + b->vrows)) ||
-           dalloc(b, &b->lc_ptr, (size_t)b->cols + 1) || dalloc(b, &b->lc_row, nl) || dalloc(b, &b->lc_ent, nl);
-  if (!rc && b->border)
-    rc = dalloc(b, &b->bc_g, (size_t)kBorderMax * kBorderMax) || dalloc(b, &b->lc_cols, (size_t)kBorderMax);
+           dalloc(b, &b->lc_ptr, (size_t)b->cols + 1) || dalloc(b, &b->lc_row, nl) || dalloc(b, &b->lc_ent, nl) ||
+           dalloc(b, &b->lc_cols, (size_t)kBorderMax);
+  if (!rc && b->border) rc = dalloc(b, &b->bc_g, (size_t)kBorderMax * kBorderMax);
   if (!rc && b->form_gen == 1) {
     b->fb_nnz = (int64_t)sy.perm_b.size();
     const size_t fz = (size_t)std::max<int64_t>(b->fb_nnz, 1);
@@ -964,7 +964,7 @@ int cols_setup(fpsq_band b, const BandSymbolic& sy) {
   }
   hipMemset(b->bd_keep, 0, (size_t)(b->mpad + b->vrows) * 8);
   hipMemcpy(b->lc_ptr, sy.lc_ptr.data(), ((size_t)b->cols + 1) * 4, hipMemcpyHostToDevice);
-  if (b->border) hipMemcpy(b->lc_cols, sy.lcols.data(), (size_t)b->cols * 4, hipMemcpyHostToDevice);
+  hipMemcpy(b->lc_cols, sy.lcols.data(), (size_t)b->cols * 4, hipMemcpyHostToDevice);
   if (!sy.lc_row.empty()) {
     hipMemcpy(b->lc_row, sy.lc_row.data(), sy.lc_row.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(b->lc_ent, sy.lc_ent.data(), sy.lc_ent.size() * 4, hipMemcpyHostToDevice);

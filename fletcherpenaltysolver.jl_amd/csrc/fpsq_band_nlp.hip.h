@@ -290,6 +290,103 @@ __global__ __launch_bounds__(256) void k_bn_jtz(const int32_t* __restrict__ t_ro
   }
 }
 
+// ---- long columns (fpsq_band_nlp_create_arrow).  In the transposed structure long column i (column j = lcols[i]) has no real
+// entries: its vgrid virtual entries gather the value 1 (ta = 1, th = 0) and point at the virtual rows mpad + 16 g + i, where
+// the solutions hold w (g = 0, zero elsewhere) and `keep` the chunk sums of U'keep.  The J' sums of the kernels above are
+// therefore complete at j; the H' sums come out 0.  These two kernels form them from h over the column's own entries, ONE
+// WORKGROUP PER LONG COLUMN behind the epilogue, and write that row's outputs again.  Sums in a fixed order (a thread's entries
+// in index order, lanes by xor shuffles, waves in index order), no atomics.
+
+// six sums of long column i over the workgroup, in thread 0: v[0 .. 2] = (J'q1)_j, (J'q2)_j, (J'keep)_j from the virtual rows,
+// v[3 .. 5] = (H'q1)_j, (H'q2)_j, (H'keep)_j from h
+__device__ __forceinline__ void bn_lc_sums(const int32_t* __restrict__ lc_ptr, const int32_t* __restrict__ lc_row,
+                                           const int32_t* __restrict__ lc_ent, const double* __restrict__ h,
+                                           const double* __restrict__ y, const double* __restrict__ keep, int mpad, int vgrid,
+                                           double (&v)[6], double* sh) {
+  const int i = blockIdx.x;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] = 0.0;
+  for (int g = threadIdx.x; g < vgrid; g += 256) {
+    const size_t row = (size_t)mpad + (size_t)kBorderMax * g + i;
+    const f64x2 t = *reinterpret_cast<const f64x2*>(y + row * 2);
+    v[0] += t.x;
+    v[1] += t.y;
+    v[2] += keep[row];
+  }
+  const int e = lc_ptr[i + 1];
+  int k = lc_ptr[i] + threadIdx.x;
+  // four entries of a thread per trip: their (dependent, gathered) loads are in flight together; the terms enter the sums in
+  // the order of the one-entry loop behind it
+  for (; k + 3 * 256 < e; k += 4 * 256) {
+    double hv[4], kv[4];
+    f64x2 t[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int p = lc_row[k + u * 256];
+      hv[u] = h[lc_ent[k + u * 256]];
+      t[u] = *reinterpret_cast<const f64x2*>(y + (size_t)p * 2);
+      kv[u] = keep[p];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      v[3] += hv[u] * t[u].x;
+      v[4] += hv[u] * t[u].y;
+      v[5] += hv[u] * kv[u];
+    }
+  }
+  for (; k < e; k += 256) {
+    const double hv = h[lc_ent[k]];
+    const int p = lc_row[k];
+    const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * 2);
+    v[3] += hv * t.x;
+    v[4] += hv * t.y;
+    v[5] += hv * keep[p];
+  }
+  bq_block_sum(v, sh);
+}
+
+// objgrad, behind k_bn_epilogue (which left qe_j = q_j, hc_j = 0 and gx_j without the curvature terms at a long column; gs_j
+// and gsm_j hold no H' sum and stay): qe_j, hc_j and gx_j by k_bn_epilogue's formulas with the sums above
+__global__ __launch_bounds__(256) void k_bn_lc_epilogue(const int32_t* __restrict__ lc_ptr, const int32_t* __restrict__ lc_row,
+                                                        const int32_t* __restrict__ lc_ent, const int32_t* __restrict__ lcols,
+                                                        const double* __restrict__ h, const double* __restrict__ y,
+                                                        const double* __restrict__ keep, const double* __restrict__ x,
+                                                        const double* __restrict__ xk, const double* __restrict__ q,
+                                                        const double* __restrict__ gsm, double sigma, double rho, double eta,
+                                                        double* __restrict__ out, double* __restrict__ qe,
+                                                        double* __restrict__ hc, int mpad, int vgrid) {
+  __shared__ double sh[24];
+  double v[6];
+  bn_lc_sums(lc_ptr, lc_row, lc_ent, h, y, keep, mpad, vgrid, v, sh);
+  if (threadIdx.x == 0) {
+    const int j = lcols[blockIdx.x];
+    const double gsv = gsm[j], p2 = -v[1];
+    const double qev = q[j] - (v[3] + sigma * v[4]);
+    const double dx = eta > 0.0 ? x[j] - (xk ? xk[j] : 0.0) : 0.0;
+    qe[j] = qev;
+    hc[j] = v[5];
+    if (out) out[j] = gsv + (sigma - qev) * p2 + v[4] * gsv + rho * v[2] + eta * dx;
+  }
+}
+
+// hprod Val(1), behind k_bn_epilogue_h1 (whose h1 is 0 at a long column): Hv_j by its formula with the sums above
+__global__ __launch_bounds__(256) void k_bn_lc_epilogue_h1(const int32_t* __restrict__ lc_ptr, const int32_t* __restrict__ lc_row,
+                                                           const int32_t* __restrict__ lc_ent, const int32_t* __restrict__ lcols,
+                                                           const double* __restrict__ h, const double* __restrict__ y,
+                                                           const double* __restrict__ keep, const double* __restrict__ vec,
+                                                           const double* __restrict__ qe, const double* __restrict__ hc,
+                                                           const double* __restrict__ gsm, double sigma, double rho, double eta,
+                                                           double* __restrict__ out, int mpad, int vgrid) {
+  __shared__ double sh[24];
+  double v[6];
+  bn_lc_sums(lc_ptr, lc_row, lc_ent, h, y, keep, mpad, vgrid, v, sh);
+  if (threadIdx.x == 0) {
+    const int j = lcols[blockIdx.x];
+    const double vv = vec[j], qv = qe[j];
+    out[j] = (qv * vv - v[1]) - qv * v[0] + 2.0 * sigma * v[0] + rho * (v[2] + hc[j] * vv) + eta * vv - v[3] * gsm[j];
+  }
+}
+
 }  // namespace fpsq
 
 // ---- host side
@@ -301,7 +398,7 @@ __global__ __launch_bounds__(256) void k_bn_jtz(const int32_t* __restrict__ t_ro
 struct fpsq_band_nlp_s {
   fpsq_band b = nullptr;
   double *q = nullptr, *d = nullptr, *bp = nullptr;  // n, n, m (b in the STORED row order)
-  double *a = nullptr, *h = nullptr, *ta = nullptr, *th = nullptr;  // nnz each
+  double *a = nullptr, *h = nullptr, *ta = nullptr, *th = nullptr;  // nnz (+ the virtual entries' slot), t_nnz
   double *qe = nullptr, *hc = nullptr, *gs = nullptr;               // q - H'ys, H'c, gs of the last successful objgrad
   double *partP = nullptr, *partE = nullptr;
   fpsq_band_qp_s lin;
@@ -319,17 +416,17 @@ int fpsq_band_nlp_destroy(fpsq_band_nlp nlp) {
   return FPSQ_OK;
 }
 
-int fpsq_band_nlp_create(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
-                         const double* h_vals, fpsq_band_nlp* out) {
-  if (!b || !qdiag || !d || !bvec || !out || (b->nnz > 0 && (!a_vals || !h_vals))) return FPSQ_ERR_ARG;
-  const char* why = b->border > 0    ? "the handle has border rows"
-                    : b->cols > 0    ? "the handle has long columns (they change the transposed structure)"
-                    : b->coo_nnz >= 0 ? "the handle was created by a fpsq_band_create_coo entry (its callers do not know the slot order)"
-                                      : nullptr;
-  if (why) {
-    b->err = std::string("band_nlp_create: ") + why;
-    return FPSQ_ERR_STATE;
-  }
+}  // extern "C"
+
+namespace {
+const char kNlpCooRefused[] =
+    "the handle was created by a fpsq_band_create_coo entry (its callers do not know the slot order)";
+
+// What the two create entries share, behind their checks of the handle's kind.  With long columns the transposed arrays span
+// t_nnz entries and gather a slot behind the stored values (a = 1, h = 0) into the virtual ones; without them t_nnz = nnz and
+// every size, lane group and launch is what it was before the handle's kind was looked at.
+int band_nlp_make(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
+                  const double* h_vals, fpsq_band_nlp* out) {
   hipSetDevice(b->device);
   if (!b->scal) {  // the scalars of a call: device side and pinned host side
     if (dalloc(b, &b->scal, 8)) return FPSQ_ERR_HIP;
@@ -344,17 +441,18 @@ int fpsq_band_nlp_create(fpsq_band b, const double* qdiag, const double* d, cons
   fpsq_band_qp_s& lin = nlp->lin;
   lin.b = b;
   lin.lgA = lane_group(b->nnz, b->m);
-  lin.lgT = lane_group(b->nnz, b->n);
+  lin.lgT = lane_group(b->t_nnz, b->n);
   lin.gridP = bq_grid(b->mpad, lin.lgA);
   lin.gridE = bq_grid(b->n, lin.lgT);
-  const size_t nb8 = (size_t)b->n * 8, mb8 = (size_t)b->m * 8, zb8 = (size_t)std::max<int64_t>(b->nnz, 1) * 8;
+  const size_t nb8 = (size_t)b->n * 8, mb8 = (size_t)b->m * 8;
+  const size_t zb8 = (size_t)(std::max<int64_t>(b->nnz, 1) + (b->cols ? 1 : 0)) * 8, tb8 = (size_t)std::max<int64_t>(b->t_nnz, 1) * 8;
   if (!qp_buffers(nlp, {{(void**)&nlp->q, nb8, qdiag, hipMemcpyDefault},
                         {(void**)&nlp->d, nb8, d, hipMemcpyDefault},
                         {(void**)&nlp->bp, mb8, bs.data(), hipMemcpyHostToDevice},
                         {(void**)&nlp->a, zb8, nullptr, hipMemcpyDefault},
                         {(void**)&nlp->h, zb8, nullptr, hipMemcpyDefault},
-                        {(void**)&nlp->ta, zb8, nullptr, hipMemcpyDefault},
-                        {(void**)&nlp->th, zb8, nullptr, hipMemcpyDefault},
+                        {(void**)&nlp->ta, tb8, nullptr, hipMemcpyDefault},
+                        {(void**)&nlp->th, tb8, nullptr, hipMemcpyDefault},
                         {(void**)&nlp->qe, nb8, nullptr, hipMemcpyDefault},
                         {(void**)&nlp->hc, nb8, nullptr, hipMemcpyDefault},
                         {(void**)&nlp->gs, nb8, nullptr, hipMemcpyDefault},
@@ -372,17 +470,26 @@ int fpsq_band_nlp_create(fpsq_band b, const double* qdiag, const double* d, cons
   // the two value arrays into both orders, by the gathers a factorisation uses for its values
   hipStream_t s = b->stream;
   const dim3 gz((unsigned)std::min<int64_t>((b->nnz + 255) / 256, 4096));
+  const dim3 gt((unsigned)std::min<int64_t>((b->t_nnz + 255) / 256, 4096));
   for (int w = 0; w < 2 && b->nnz > 0; ++w) {
     const double* src = w ? h_vals : a_vals;
     double *st = w ? nlp->h : nlp->a, *tr = w ? nlp->th : nlp->ta;
     hipError_t e;
+    if (b->cols) {  // the slot the virtual entries gather (nothing is in flight on the array yet)
+      const double slot = w ? 0.0 : 1.0;
+      if (hipMemcpy(st + b->nnz, &slot, 8, hipMemcpyHostToDevice) != hipSuccess) {
+        b->err = "band_nlp_create: cannot read the constraint values";
+        fpsq_band_nlp_destroy(nlp);
+        return FPSQ_ERR_HIP;
+      }
+    }
     if (b->reordered) {
       e = hipMemcpyAsync(b->vals_in, src, (size_t)b->nnz * 8, hipMemcpyDefault, s);
       hipLaunchKernelGGL(k_gather_d, gz, dim3(256), 0, s, b->vals_in, b->vperm, st, b->nnz);
     } else {
       e = hipMemcpyAsync(st, src, (size_t)b->nnz * 8, hipMemcpyDefault, s);
     }
-    hipLaunchKernelGGL(k_gather_d, gz, dim3(256), 0, s, st, b->t_perm, tr, b->nnz);
+    hipLaunchKernelGGL(k_gather_d, gt, dim3(256), 0, s, st, b->t_perm, tr, b->t_nnz);
     if (e != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
       b->err = "band_nlp_create: cannot read the constraint values";
       fpsq_band_nlp_destroy(nlp);
@@ -391,6 +498,33 @@ int fpsq_band_nlp_create(fpsq_band b, const double* qdiag, const double* d, cons
   }
   *out = nlp;
   return FPSQ_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fpsq_band_nlp_create(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
+                         const double* h_vals, fpsq_band_nlp* out) {
+  if (!b || !qdiag || !d || !bvec || !out || (b->nnz > 0 && (!a_vals || !h_vals))) return FPSQ_ERR_ARG;
+  const char* why = b->border > 0    ? "the handle has border rows"
+                    : b->cols > 0    ? "the handle has long columns (they change the transposed structure)"
+                    : b->coo_nnz >= 0 ? kNlpCooRefused
+                                      : nullptr;
+  if (why) {
+    b->err = std::string("band_nlp_create: ") + why;
+    return FPSQ_ERR_STATE;
+  }
+  return band_nlp_make(b, qdiag, d, bvec, a_vals, h_vals, out);
+}
+
+int fpsq_band_nlp_create_arrow(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
+                               const double* h_vals, fpsq_band_nlp* out) {
+  if (!b || !qdiag || !d || !bvec || !out || (b->nnz > 0 && (!a_vals || !h_vals))) return FPSQ_ERR_ARG;
+  if (b->coo_nnz >= 0) {
+    b->err = std::string("band_nlp_create_arrow: ") + kNlpCooRefused;
+    return FPSQ_ERR_STATE;
+  }
+  return band_nlp_make(b, qdiag, d, bvec, a_vals, h_vals, out);
 }
 
 int fpsq_band_nlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* c) {
@@ -431,6 +565,9 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
                        b->colind, ax.tile(), b->vals, b->nnz);
     WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_tvals<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, nlp->ta, nlp->th,
                                                 ax.tile(), b->t_vals, n))
+    if (b->fb_nnz > 0)  // (long columns and k_band_form: the values of the other columns alone, as fpsq_band_factorize)
+      hipLaunchKernelGGL(k_gather_d, dim3((unsigned)std::min<int64_t>((b->fb_nnz + 255) / 256, 4096)), dim3(256), 0, s, b->vals,
+                         b->fb_perm, b->fb_vals, b->fb_nnz);
   }
   // 2: the numeric factorisation on them
   if (int rc = band_factor_numeric(b, delta, info)) return rc;  // (1: no valid factor, *info says where; nothing is evaluated)
@@ -438,16 +575,21 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
   if (int rc = eval_begin(b)) return rc;
   const StagedArg ogx = staged(b, gx, b->o_p1, (size_t)n), ogs = staged(b, gs, b->o_p2, (size_t)n),
                   oys = staged(b, ys, b->o_q1, (size_t)m);
-  double* keep = b->o_q2;
+  double* keep = b->cols ? b->bd_keep : b->o_q2;  // (long columns: the operand has virtual rows, as in bq_launches)
   hipLaunchKernelGGL(k_bq_pack<false>, grid256(n), dim3(256), 0, s, ax.tile(), nlp->q, nlp->d, b->xn, n);
   WITH_LANE_GROUP(lin.lgA, hipLaunchKernelGGL(k_bn_prologue<LG>, dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals,
                                               nlp->h, b->xn, ax.tile(), nlp->q, nlp->d, nlp->bp, b->r2, keep, nlp->partP, m, mpad,
                                               n))
+  if (b->cols) cols_keep<1>(b, keep);
   band_solve(b);
   WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_epilogue<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind,
                                               b->t_vals, nlp->th, b->r2, keep, b->row_perm(), ax.tile(), axk.tile(), nlp->q, nlp->d,
                                               sigma, rho, eta, ogx.tile(), ogs.tile(), oys.tile(), nlp->qe, nlp->hc, nlp->gs,
                                               nlp->partE, n, m))
+  if (b->cols)  // the curvature sums at the long columns, whose transposed rows are virtual
+    hipLaunchKernelGGL(k_bn_lc_epilogue, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->lc_cols, nlp->h,
+                       b->r2, keep, ax.tile(), axk.tile(), nlp->q, nlp->gs, sigma, rho, eta, ogx.tile(), nlp->qe, nlp->hc, mpad,
+                       b->bc_grid);
   hipLaunchKernelGGL(k_bq_phi, dim3(1), dim3(256), 0, s, nlp->partP, lin.gridP, nlp->partE, lin.gridE, rho, eta, b->scal);
   for (const StagedArg* o : {&ogx, &ogs, &oys})
     if (int rc = stage_back(b, *o)) return rc;
@@ -486,15 +628,19 @@ int fpsq_band_nlp_hprod(fpsq_band b, fpsq_band_nlp nlp, const double* v, double 
     bq_launches(b, &lin, true, av.tile(), nullptr, sigma, rho, eta, ah.tile(), nullptr, nullptr);
     if (rho > 0.0) hipLaunchKernelGGL(k_bn_hcv, grid256(n), dim3(256), 0, s, nlp->hc, av.tile(), ah.tile(), n);
   } else {
-    double* keep = b->o_q2;
+    double* keep = b->cols ? b->bd_keep : b->o_q2;
     hipLaunchKernelGGL(k_bq_pack<true>, grid256(n), dim3(256), 0, s, av.tile(), nlp->qe, nlp->d, b->xn, n);
     WITH_LANE_GROUP(lin.lgA, hipLaunchKernelGGL((k_bq_prologue<LG, true, false>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr,
                                                 b->colind, b->vals, b->xn, av.tile(), nlp->qe, nlp->d, nlp->bp, b->r2, keep,
                                                 nlp->partP, m, mpad, n))
+    if (b->cols) cols_keep<1>(b, keep);
     band_solve(b);
     WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_epilogue_h1<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind,
                                                 b->t_vals, nlp->th, b->r2, keep, av.tile(), nlp->qe, nlp->hc, nlp->gs, sigma, rho,
                                                 eta, ah.tile(), n))
+    if (b->cols)  // (H'q1)_j at the long columns, before the second solve takes b->r2
+      hipLaunchKernelGGL(k_bn_lc_epilogue_h1, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->lc_cols, nlp->h,
+                         b->r2, keep, av.tile(), nlp->qe, nlp->hc, nlp->gs, sigma, rho, eta, ah.tile(), mpad, b->bc_grid);
     // z = M^-1 H (gs .* v) on the cached factor (tau = delta, include/fpsq.h), Hv -= J'z
     WITH_LANE_GROUP(lin.lgA, hipLaunchKernelGGL(k_bn_hgv<LG>, dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, nlp->h,
                                                 nlp->gs, av.tile(), b->r2, m, mpad))

@@ -435,9 +435,15 @@ class DeviceBandSepQuadNLP:
     and refactorises J J' + delta I (`info()["factorizations"]` counts them); `hprod` runs at the point of the last objgrad, on
     its factor, and the two `hessian_approx` modes differ.  `objgrad` / `hprod` have DeviceBandEqQP's parameter lists;
     `fps_solve_device` takes the object (`nonlinear = True` selects the penalty wrapper that keeps track of that point).
-    `qp` is the underlying EqQP (objective, pattern, x, xhat)."""
+    `qp` is the underlying EqQP (objective, pattern, x, xhat).
+    `_create_entry`, `_limits`, `_model_entry` (class attributes): the C entry that creates the handle, the (max_border,
+    max_cols) it takes behind the pattern (none: `fpsq_band_create`), and the entry that creates the model on it
+    (DeviceArrowBandSepQuadNLP names `fpsq_band_create_arrow` and `fpsq_band_nlp_create_arrow`)."""
 
     nonlinear = True
+    _create_entry = "fpsq_band_create"
+    _limits = ()
+    _model_entry = "fpsq_band_nlp_create"
 
     def __init__(self, nlp_data, sigma=1e3, rho=1.0, delta=0.0, eta=0.0, device=0, ldlt_tol=None, ldlt_r2=None):
         from .qdsolver import _ldlt_r2
@@ -453,7 +459,8 @@ class DeviceBandSepQuadNLP:
         rp = np.ascontiguousarray(qp.rowptr, dtype=np.int32)
         ci = np.ascontiguousarray(qp.colind, dtype=np.int32)
         h = C.c_void_p()
-        if self._lib.fpsq_band_create(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data, self.device) != 0:
+        if getattr(self._lib, self._create_entry)(C.byref(h), qp.n, qp.m, rp.ctypes.data, ci.ctypes.data,
+                                                  *(int(v) for v in self._limits), self.device) != 0:
             raise FpsqError(self._lib.fpsq_band_last_error(None).decode())
         self._h = h
         try:
@@ -463,9 +470,9 @@ class DeviceBandSepQuadNLP:
             self._check(self._lib.fpsq_band_set_regularization(h, self.ldlt_tol, -self.ldlt_r2))
             f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
             q = C.c_void_p()
-            self._check(self._lib.fpsq_band_nlp_create(h, f64(qp.qdiag).ctypes.data, f64(qp.d).ctypes.data,
-                                                       f64(nlp_data.b).ctypes.data, f64(qp.vals).ctypes.data,
-                                                       f64(nlp_data.hvals).ctypes.data, C.byref(q)))
+            self._check(getattr(self._lib, self._model_entry)(h, f64(qp.qdiag).ctypes.data, f64(qp.d).ctypes.data,
+                                                              f64(nlp_data.b).ctypes.data, f64(qp.vals).ctypes.data,
+                                                              f64(nlp_data.hvals).ctypes.data, C.byref(q)))
             self._q = q
         except Exception:
             self.close()
@@ -528,6 +535,22 @@ class DeviceBandSepQuadNLP:
             self.close()
         except Exception:
             pass
+
+
+class DeviceArrowBandSepQuadNLP(DeviceBandSepQuadNLP):
+    """DeviceBandSepQuadNLP on an ARROW band: at most `border` long constraint rows and at most `cols` long columns (both
+    0 .. 16, independently; include/fpsq.h "ARROW BAND") stay out of the band of J J' + delta I -- a nonlinear model with a
+    free final time or a global parameter and an integral, mean-value or mass constraint.  The handle comes from
+    `fpsq_band_create_arrow`, the model from `fpsq_band_nlp_create_arrow`; every method is the base class's.
+    `info()["border_rows"]` and `info()["border_cols"]` say what was taken; `border=0` or `cols=0` gives the handle of one
+    kind, both the plain one.  The other keywords are DeviceBandSepQuadNLP's (whose parameter list stays as it is)."""
+
+    _create_entry = "fpsq_band_create_arrow"
+    _model_entry = "fpsq_band_nlp_create_arrow"
+
+    def __init__(self, nlp_data, border=16, cols=16, **kwargs):
+        self._limits = (int(border), int(cols))
+        super().__init__(nlp_data, **kwargs)
 
 
 def rccl_unique_id() -> bytes:

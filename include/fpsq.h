@@ -576,6 +576,19 @@ int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
  *                         or long columns are accepted, reordered and two-chain ones included; a handle with border rows, with
  *                         long columns (they change the transposed structure) or created by a fpsq_band_create_coo* entry (its
  *                         callers do not know the slot order) gives FPSQ_ERR_STATE and a message that names which.
+ *   fpsq_band_nlp_create_arrow  the same parameter list for a handle of ANY kind but the last: border rows, long columns, both
+ *                         (fpsq_band_create_bordered, _create_bordered_cols, _create_arrow) or neither (then the model gives
+ *                         the bits of fpsq_band_nlp_create's); only a handle of a fpsq_band_create_coo* entry is refused
+ *                         (FPSQ_ERR_STATE, the same message).  Every entry below takes the model whichever entry made it, with
+ *                         the same state rules and soft codes; a failing border pivot in an objgrad's factorisation is reported
+ *                         or regularised exactly as fpsq_band_factorize does on that handle.  Border rows cost nothing beyond
+ *                         the handle's own correction of an M-solve.  With long columns the transposed value arrays gain the
+ *                         virtual entries of "LONG COLUMNS" (J': 1, H': 0), and an objgrad / an hprod Val(1) adds two launches: the chunk
+ *                         sums of U'c resp. U'(J v) into the virtual rows (as fpsq_band_qp_objgrad has them), and one workgroup
+ *                         per long column that forms (H'q1)_j, (H'q2)_j, (H'c)_j from the column's own entries in a fixed order
+ *                         and completes gx_j, (q - H'ys)_j, (H'c)_j resp. Hv_j -- the transposed rows of a long column are
+ *                         virtual and carry no curvature.  An objgrad adds a third when the band is formed by row pairs
+ *                         (FPSQ_BAND_FORM=1: the gather of the other columns' values).  hprod Val(2) adds none.
  *   fpsq_band_nlp_objgrad one `objgrad!` at a fresh x: (1) J(x) is written into the handle's value arrays; (2) the numeric
  *                         factorisation of J J' + delta I runs on them -- the return value is the soft code 1 with *info (may be
  *                         NULL) as fpsq_band_factorize gives them, and with it nothing is evaluated and no output is written;
@@ -605,6 +618,8 @@ int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
 typedef struct fpsq_band_nlp_s *fpsq_band_nlp;
 int fpsq_band_nlp_create(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
                          const double *h_vals, fpsq_band_nlp *out);
+int fpsq_band_nlp_create_arrow(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
+                               const double *h_vals, fpsq_band_nlp *out);
 int fpsq_band_nlp_destroy(fpsq_band_nlp nlp);
 int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double *x, double sigma, double rho, double eta, double delta,
                           const double *xk, double *fx, double *gx, double *ys, double *gs, int32_t *info);
