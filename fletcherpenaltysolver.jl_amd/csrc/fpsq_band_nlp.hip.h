@@ -391,12 +391,25 @@ __global__ __launch_bounds__(256) void k_bn_lc_epilogue_h1(const int32_t* __rest
 
 // ---- host side
 
+// What a model with coupling terms (fpsq_band_nlp_create_coupled, fpsq_band_cnlp.hip.h) holds besides fpsq_band_nlp_s' own arrays:
+// the lists of fpsq_coupled.h on the device -- partner lists of the stored and of the transposed entries, the latter's own
+// columns, the contributor lists of S -- and the values of Wo(q2), Wo(c) on S.  S itself, -Wo(ys) and the n-vector tv (p2 resp.
+// Ptv) are the `lin` view's r_rowptr / r_colind / r_vals / tv.  The buffers are on the model's list.
+struct fpsq_band_cnlp_s {
+  int32_t *pptr = nullptr, *pcol = nullptr, *tpptr = nullptr, *tpcol = nullptr, *tcol = nullptr;
+  double *pw = nullptr, *tpw = nullptr;
+  int32_t *cptr = nullptr, *crow = nullptr;
+  double *cw = nullptr, *wq2 = nullptr, *wc = nullptr;
+  int64_t snz = 0;
+};
+
 // fpsq_band_nlp_create: the model's vectors and its two value arrays in the stored row order (a, h: through vperm) and in the
 // transposed order (ta, th: through t_perm), gathered once; the three n-vectors an objgrad leaves for the Hessian products;
 // `lin`: the view fpsq_band_qp's unchanged kernels take for hprod Val(2) (q = qe).  It borrows the handle's buffers as
 // fpsq_band_qp_s does.
 struct fpsq_band_nlp_s {
   fpsq_band b = nullptr;
+  fpsq_band_cnlp_s* cp = nullptr;  // non-null: the model has coupling terms and runs fpsq_band_cnlp.hip.h's launches
   double *q = nullptr, *d = nullptr, *bp = nullptr;  // n, n, m (b in the STORED row order)
   double *a = nullptr, *h = nullptr, *ta = nullptr, *th = nullptr;  // nnz (+ the virtual entries' slot), t_nnz
   double *qe = nullptr, *hc = nullptr, *gs = nullptr;               // q - H'ys, H'c, gs of the last successful objgrad
@@ -412,6 +425,7 @@ extern "C" {
 int fpsq_band_nlp_destroy(fpsq_band_nlp nlp) {
   if (!nlp) return FPSQ_ERR_ARG;
   for (void* p : nlp->allocs) hipFree(p);
+  delete nlp->cp;
   delete nlp;
   return FPSQ_OK;
 }
@@ -499,6 +513,13 @@ int band_nlp_make(fpsq_band b, const double* qdiag, const double* d, const doubl
   *out = nlp;
   return FPSQ_OK;
 }
+
+// a model with coupling terms (nlp->cp): fpsq_band_cnlp.hip.h
+int band_cnlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* c);
+int band_cnlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, double sigma, double rho, double eta, double delta,
+                      const double* xk, double* fx, double* gx, double* ys, double* gs, int32_t* info);
+void band_cnlp_hprod_launches(fpsq_band b, fpsq_band_nlp nlp, const double* v, double sigma, double rho, double eta,
+                              int32_t hessian_approx, double* Hv);
 }  // namespace
 
 extern "C" {
@@ -529,6 +550,7 @@ int fpsq_band_nlp_create_arrow(fpsq_band b, const double* qdiag, const double* d
 
 int fpsq_band_nlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* c) {
   if (!b || !nlp || nlp->b != b || !x || !c) return FPSQ_ERR_ARG;
+  if (nlp->cp) return band_cnlp_cons(b, nlp, x, c);
   hipSetDevice(b->device);
   if (int rc = wait_input(b)) return rc;
   const StagedArg ax = staged(b, x, b->in_a, (size_t)b->n);
@@ -545,6 +567,7 @@ int fpsq_band_nlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* 
 int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, double sigma, double rho, double eta, double delta,
                           const double* xk, double* fx, double* gx, double* ys, double* gs, int32_t* info) {
   if (!b || !nlp || nlp->b != b || !x || !fx || !(delta >= 0.0)) return FPSQ_ERR_ARG;
+  if (nlp->cp) return band_cnlp_objgrad(b, nlp, x, sigma, rho, eta, delta, xk, fx, gx, ys, gs, info);
   hipSetDevice(b->device);
   hipStream_t s = b->stream;
   const fpsq_band_qp_s& lin = nlp->lin;
@@ -624,7 +647,9 @@ int fpsq_band_nlp_hprod(fpsq_band b, fpsq_band_nlp nlp, const double* v, double 
   const StagedArg av = staged(b, v, b->in_a, (size_t)n);
   if (int rc = stage_in(b, av)) return rc;
   const StagedArg ah = staged(b, Hv, b->o_p1, (size_t)n);
-  if (hessian_approx == 2) {  // the linear model's launches with q = qe, then the curvature of rho/2 |c|^2
+  if (nlp->cp) {
+    band_cnlp_hprod_launches(b, nlp, av.tile(), sigma, rho, eta, hessian_approx, ah.tile());
+  } else if (hessian_approx == 2) {  // the linear model's launches with q = qe, then the curvature of rho/2 |c|^2
     bq_launches(b, &lin, true, av.tile(), nullptr, sigma, rho, eta, ah.tile(), nullptr, nullptr);
     if (rho > 0.0) hipLaunchKernelGGL(k_bn_hcv, grid256(n), dim3(256), 0, s, nlp->hc, av.tile(), ah.tile(), n);
   } else {

@@ -470,9 +470,9 @@ class DeviceBandSepQuadNLP:
             self._check(self._lib.fpsq_band_set_regularization(h, self.ldlt_tol, -self.ldlt_r2))
             f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
             q = C.c_void_p()
-            self._check(getattr(self._lib, self._model_entry)(h, f64(qp.qdiag).ctypes.data, f64(qp.d).ctypes.data,
-                                                              f64(nlp_data.b).ctypes.data, f64(qp.vals).ctypes.data,
-                                                              f64(nlp_data.hvals).ctypes.data, C.byref(q)))
+            keep = [f64(a) for a in (qp.qdiag, qp.d, nlp_data.b, qp.vals, nlp_data.hvals)] + list(self._model_extra(nlp_data))
+            self._check(getattr(self._lib, self._model_entry)(h, *(a.ctypes.data if isinstance(a, np.ndarray) else a
+                                                                   for a in keep), C.byref(q)))
             self._q = q
         except Exception:
             self.close()
@@ -480,6 +480,10 @@ class DeviceBandSepQuadNLP:
 
     _check = DeviceBandEqQP._check
     _order = DeviceBandEqQP._order
+
+    def _model_extra(self, nlp_data):
+        """what `_model_entry` takes between h_vals and the model's address: numpy arrays (kept alive over the call) or scalars"""
+        return ()
 
     def set_delta(self, delta):
         """The delta of the NEXT objgrad's factorisation (an hprod stays on the factor of the last one)."""
@@ -551,6 +555,21 @@ class DeviceArrowBandSepQuadNLP(DeviceBandSepQuadNLP):
     def __init__(self, nlp_data, border=16, cols=16, **kwargs):
         self._limits = (int(border), int(cols))
         super().__init__(nlp_data, **kwargs)
+
+
+class DeviceBandCoupledQuadNLP(DeviceBandSepQuadNLP):
+    """DeviceBandSepQuadNLP with COUPLING TERMS w x_j x_k between columns of a constraint row (`nlp_data`: a
+    `problems.CoupledQuadNLP` -- `problems.with_coupled_constraints`, `problems.bilinear_control_like`; host view:
+    `nlpmodels.CoupledQuadConModel`): a state times a control, a state times a parameter.  The model comes from
+    `fpsq_band_nlp_create_coupled` (include/fpsq.h); every method is the base class's, and `fps_solve_device` takes the object
+    unchanged.  Without terms the model is DeviceBandSepQuadNLP's, bit for bit."""
+
+    _model_entry = "fpsq_band_nlp_create_coupled"
+
+    def _model_extra(self, nlp_data):
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+        return (C.c_int64(int(nlp_data.t_w.size)), i32(nlp_data.t_row), i32(nlp_data.t_j), i32(nlp_data.t_k),
+                np.ascontiguousarray(nlp_data.t_w, dtype=np.float64))
 
 
 def rccl_unique_id() -> bytes:

@@ -303,6 +303,60 @@ class SepQuadConModel(EqQPModel):
     def ghjvprod(self, x, g, v): return self._H @ (np.asarray(g) * np.asarray(v))
 
 
+class CoupledQuadConModel(SepQuadConModel):
+    """Host view of problems.CoupledQuadNLP: SepQuadConModel plus the coupling terms w_t x_jt x_kt in c_trow.  J(x) gains
+    w_t x_kt at (row, jt) and w_t x_jt at (row, kt) -- entries of the pattern --, sum_i y_i Hess c_i = diag(H'y) + Wo(y) with
+    Wo(y) = sum_t w_t y_trow (e_jt e_kt' + e_kt e_jt'), and ghjvprod(x, g, v)_i gains sum_{t in i} w_t (g_jt v_kt + g_kt v_jt)."""
+
+    def __init__(self, data):
+        import scipy.sparse as sp
+
+        super().__init__(data)
+        qp = data.qp
+        self.t_row, self.t_j, self.t_k = (np.asarray(a, dtype=np.int64) for a in (data.t_row, data.t_j, data.t_k))
+        self.t_w = np.ascontiguousarray(data.t_w, dtype=np.float64)
+        # the CSR position of (row, column) by a lookup in the sorted keys row * n + column
+        rows = np.repeat(np.arange(qp.m, dtype=np.int64), np.diff(qp.rowptr))
+        keys = rows * qp.n + qp.colind.astype(np.int64)
+        order = np.argsort(keys, kind="stable")
+
+        def entry(r, c):
+            want = r * qp.n + c
+            pos = np.searchsorted(keys[order], want)
+            assert np.all(pos < keys.size) and np.array_equal(keys[order][np.minimum(pos, keys.size - 1)], want), \
+                "a coupling term lies off the pattern of A"
+            return order[pos]
+
+        self._ej, self._ek = entry(self.t_row, self.t_j), entry(self.t_row, self.t_k)
+        self._sp = sp
+        self.meta.name = qp.name + "-coupled"
+
+    def _Wo(self, y):
+        """Wo(y): n x n, symmetric, zero diagonal"""
+        n, wy = self.qp.n, self.t_w * np.asarray(y, float)[self.t_row]
+        return self._sp.coo_matrix((np.concatenate([wy, wy]), (np.concatenate([self.t_j, self.t_k]),
+                                                               np.concatenate([self.t_k, self.t_j]))), shape=(n, n)).tocsr()
+
+    def cons(self, x):
+        x = np.asarray(x, float)
+        return super().cons(x) + np.bincount(self.t_row, self.t_w * x[self.t_j] * x[self.t_k], self.qp.m)
+
+    def jac_coord(self, x):
+        x = np.asarray(x, float)
+        vals = super().jac_coord(x).copy()
+        np.add.at(vals, self._ej, self.t_w * x[self.t_k])
+        np.add.at(vals, self._ek, self.t_w * x[self.t_j])
+        return vals
+
+    def hprod(self, x, y, v, obj_weight=1.0):
+        return super().hprod(x, y, v, obj_weight) + self._Wo(y) @ np.asarray(v, float)
+
+    def ghjvprod(self, x, g, v):
+        g, v = np.asarray(g, float), np.asarray(v, float)
+        return super().ghjvprod(x, g, v) + np.bincount(
+            self.t_row, self.t_w * (g[self.t_j] * v[self.t_k] + g[self.t_k] * v[self.t_j]), self.qp.m)
+
+
 class TorchEqQPModel(EqQPModel):
     """The same model with its Jacobian RESIDENT ON THE GPU (torch): `jac_coord` returns a device tensor, which the direct
     back-ends take in place (fpsq_dense_set_jacobian_coo / fpsq_band_factorize_coo: no Jacobian value crosses PCIe), and

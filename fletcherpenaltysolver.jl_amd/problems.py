@@ -231,6 +231,86 @@ def with_quadratic_constraints(qp: EqQP, curv: float = 0.1, seed: int = 0) -> Se
     return SepQuadNLP(qp, np.ascontiguousarray(hvals, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64))
 
 
+@dataclass
+class CoupledQuadNLP(SepQuadNLP):
+    """A SepQuadNLP plus coupling terms t = (t_row, t_j, t_k, t_w), each adding t_w x_tj x_tk to c_trow (0-based, t_j != t_k):
+    c_i(x) = sum_j (A_ij + 1/2 H_ij x_j) x_j + sum_{t in i} w_t x_jt x_kt - b_i.  Both columns of a term are entries of its row of
+    A (an explicit zero where need be), so J(x) keeps the pattern (nlpmodels.CoupledQuadConModel, include/fpsq.h
+    fpsq_band_nlp_create_coupled)."""
+
+    t_row: np.ndarray = None  # int32
+    t_j: np.ndarray = None    # int32
+    t_k: np.ndarray = None    # int32
+    t_w: np.ndarray = None    # float64
+
+    @property
+    def nterms(self) -> int:
+        return int(self.t_w.size)
+
+
+def _coupled(qp, hvals, t_row, t_j, t_k, t_w) -> CoupledQuadNLP:
+    """the model with b set so that xhat is feasible"""
+    import scipy.sparse as sp
+
+    xh = qp.xhat
+    H = sp.csr_matrix((hvals, qp.colind, qp.rowptr), shape=(qp.m, qp.n))
+    b = qp.scipy_csr() @ xh + 0.5 * (H @ (xh * xh)) + np.bincount(t_row, t_w * xh[t_j] * xh[t_k], qp.m)
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)  # noqa: E731
+    return CoupledQuadNLP(qp, f64(hvals), f64(b), i32(t_row), i32(t_j), i32(t_k), f64(t_w))
+
+
+def with_coupled_constraints(qp: EqQP, curv: float = 0.1, pairs: int = 2, seed: int = 0, rows=None) -> CoupledQuadNLP:
+    """`with_quadratic_constraints(qp, curv, seed)` (the same draw of hvals) plus up to `pairs` coupling terms per row, between
+    columns of that row.  A row with entries e_0 < ... < e_{L-1} has the candidates, in this order: its first `pairs` - 1
+    neighbouring pairs (e_0, e_1), (e_1, e_2), ..., then (e_0, e_{L-1}) when L > 2, then the remaining neighbouring pairs; the
+    first `pairs` of them are taken (a row of one entry has none).  Weights: curv sqrt|a_j a_k| U(0.5, 1.5) (+-1), drawn after
+    the hvals from the same generator, one of each per term in row order.  `rows` (a boolean mask or an index array, default
+    all) restricts the rows that get terms.  b is set so that xhat stays feasible."""
+    sep = with_quadratic_constraints(qp, curv, seed)
+    rng = np.random.default_rng(seed)
+    rng.uniform(0.5, 1.5, qp.vals.size), rng.choice([-1.0, 1.0], qp.vals.size)  # (the draws of the hvals)
+    take = np.zeros(qp.m, dtype=bool)
+    take[np.arange(qp.m) if rows is None else rows] = True
+    t_row, e_j, e_k = [], [], []
+    for i in np.flatnonzero(take):
+        lo, L = int(qp.rowptr[i]), int(qp.rowptr[i + 1] - qp.rowptr[i])
+        nb = [(u, u + 1) for u in range(L - 1)]
+        cand = nb[:max(pairs - 1, 0)] + ([(0, L - 1)] if L > 2 else []) + nb[max(pairs - 1, 0):]
+        for u, v in cand[:pairs]:
+            t_row.append(i), e_j.append(lo + u), e_k.append(lo + v)
+    t_row, e_j, e_k = (np.asarray(a, dtype=np.int64) for a in (t_row, e_j, e_k))
+    t_w = (curv * np.sqrt(np.abs(qp.vals[e_j] * qp.vals[e_k])) * rng.uniform(0.5, 1.5, t_row.size)
+           * rng.choice([-1.0, 1.0], t_row.size))
+    return _coupled(qp, sep.hvals, t_row, qp.colind[e_j], qp.colind[e_k], t_w)
+
+
+def bilinear_control_like(N=2000, tau=0.25, alpha=0.1, seed=1234) -> CoupledQuadNLP:
+    """Bilinear control of y' = -y + u y + s by explicit Euler steps of length tau: states y_0 .. y_N, controls
+    u_0 .. u_{N-1}, interleaved x = (y_0, u_0, y_1, u_1, ..., y_N) (n = 2 N + 1, a band of width 3), rows k = 0 .. N - 1
+        y_{k+1} - y_k + tau y_k - tau u_k y_k = b_k,
+    objective 1/2 sum (y - yhat)^2 + alpha/2 sum u^2 (up to its constant): q = 1 on the states, alpha on the controls,
+    d = -yhat on the states.  Three entries per row -- (k, y_k) = tau - 1, (k, u_k) = 0 stored EXPLICITLY so that the term lies on
+    the pattern, (k, y_{k+1}) = 1 -- no separable curvature, and one coupling term (k, y_k, u_k, -tau) per row.  yhat = 1 +
+    0.5 sin(2 pi k / N); xhat: states 1 + 0.3 (2u - 1), controls 0.5 (2u - 1) from the counter-based generator; b (the source
+    s) makes xhat feasible; x = xhat + 0.1 (2u - 1)."""
+    n, m = 2 * N + 1, N
+    k = np.arange(N, dtype=np.int64)
+    rowptr = 3 * np.arange(m + 1, dtype=np.int64)
+    colind = np.stack([2 * k, 2 * k + 1, 2 * k + 2], axis=1).ravel()
+    vals = np.tile(np.array([tau - 1.0, 0.0, 1.0]), N)
+    idx = np.arange(n, dtype=np.int64)
+    state = idx % 2 == 0
+    qdiag = np.where(state, 1.0, alpha)
+    yhat = 1.0 + 0.5 * np.sin(2.0 * np.pi * (idx // 2) / N)
+    d = np.where(state, -yhat, 0.0)
+    xhat = np.where(state, 1.0 + 0.3 * (2.0 * uniform01(seed, idx, 3) - 1.0), 0.5 * (2.0 * uniform01(seed, idx, 3) - 1.0))
+    x = xhat + 0.1 * (2.0 * uniform01(seed, idx, 4) - 1.0)
+    qp = EqQP(f"bilinear-control-N{N}", n, m, rowptr.astype(np.int32), colind.astype(np.int32), vals, qdiag, d,
+              np.zeros(m), x, xhat)   # (qp.b is the LINEAR constraints' and is not used)
+    return _coupled(qp, np.zeros_like(vals), k, 2 * k, 2 * k + 1, np.full(N, -float(tau)))
+
+
 def _stratified_rows(m, n, per_row, start, width, seed, diag_col=None, diag_boost=0.0):
     """Each of the m rows gets `per_row` sorted, distinct columns: one per stratum of
     [start[i], start[i] + width).  If diag_col is given, the stratum containing diag_col[i] is

@@ -614,12 +614,40 @@ int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
  *                         handle since (fpsq_band_factorize[_coo], another model's objgrad): FPSQ_ERR_STATE with a message -- the
  *                         handle counts its factorisations and the model remembers the count it saw.
  *   fpsq_band_nlp_cons    c(x) in the caller's row order: one launch on the model's own arrays, no factor needed.
+ *   fpsq_band_nlp_create_coupled  the same model with COUPLING TERMS: nterms terms t = (t_row, t_j, t_k, t_w), each adding
+ *                         t_w x_tj x_tk to c_trow, so that with "t in i" for t_row = i
+ *                           c_i(x)  = sum_j (A_ij + 1/2 H_ij x_j) x_j + sum_{t in i} w_t x_jt x_kt - b_i,
+ *                           J(x)_ij = A_ij + H_ij x_j + sum_{t in i, jt = j} w_t x_kt + sum_{t in i, kt = j} w_t x_jt,
+ *                           sum_i y_i Hess c_i = diag(H'y) + Wo(y),  Wo(y)_jk = Wo(y)_kj = sum_{t: {jt, kt} = {j, k}} w_t y_trow,
+ *                           ghjvprod(x, g, v)_i = sum_j H_ij g_j v_j + sum_{t in i} w_t (g_jt v_kt + g_kt v_jt).
+ *                         t_row: 0-based rows in the caller's order; t_j, t_k: 0-based columns, BOTH entries of row t_row of the
+ *                         handle's pattern (store an explicit A_ij = 0 where need be), so J(x) keeps the pattern and the symbolic
+ *                         phase, the orderings and the factorisation are those of the handle.  Host or device pointers; all are
+ *                         copied.  The terms are checked once, on the host: an index out of range, jt = kt (a square belongs to
+ *                         h_vals), a pair {j, k} listed twice in a row (in either order), a (row, j) or (row, k) that is not an
+ *                         entry of the pattern give FPSQ_ERR_ARG with a message.  Handles as fpsq_band_nlp_create takes them
+ *                         (border rows, long columns, _coo: FPSQ_ERR_STATE with its messages).  The entries above take the model,
+ *                         with the same state rules and soft codes, and compute fpsq_band_nlp_objgrad's / _hprod's formulas with
+ *                         diag(H'y) + Wo(y) in the place of diag(H'y) everywhere: with E = diag(q - H'ys) - Wo(ys),
+ *                           gx = gs - E p2 + sigma p2 + (diag(H'q2) + Wo(q2)) gs + rho J'c + eta (x - xk),
+ *                           Val(2): (p1, _, p2, _) = solve_two_least_squares(v, E v), Hv = p2 - E Ptv + 2 sigma Ptv
+ *                                   [+ (diag(H'c) + Wo(c)) v + rho J'(J v)] [+ eta v],
+ *                           Val(1): the same with rho ((diag(H'c) + Wo(c)) v + J'(J v)), and
+ *                                   Hv -= J'z + (diag(H'q1) + Wo(q1)) gs,  z = M^-1 ghjvprod(x, gs, v).
+ *                         With nterms = 0 (the term pointers may be NULL) the model IS fpsq_band_nlp_create's: the same launches,
+ *                         the same bits.  With terms an objgrad is 8 launches besides the factorisation and the sweeps (the
+ *                         separable model: 6), hprod Val(2) 4 or 5 (3 or 4), Val(1) 6 (5); S = the pattern of Wo, its contributor
+ *                         lists and the per-entry partner lists are built at create.
  * Destroy a model before the handle it was created on. */
 typedef struct fpsq_band_nlp_s *fpsq_band_nlp;
 int fpsq_band_nlp_create(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
                          const double *h_vals, fpsq_band_nlp *out);
 int fpsq_band_nlp_create_arrow(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
                                const double *h_vals, fpsq_band_nlp *out);
+int fpsq_band_nlp_create_coupled(fpsq_band b, const double *qdiag, const double *d, const double *bvec,
+                                 const double *a_vals, const double *h_vals,
+                                 int64_t nterms, const int32_t *t_row, const int32_t *t_j, const int32_t *t_k,
+                                 const double *t_w, fpsq_band_nlp *out);
 int fpsq_band_nlp_destroy(fpsq_band_nlp nlp);
 int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double *x, double sigma, double rho, double eta, double delta,
                           const double *xk, double *fx, double *gx, double *ys, double *gs, int32_t *info);
