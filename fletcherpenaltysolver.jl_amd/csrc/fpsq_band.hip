@@ -1,7 +1,7 @@
 // fpsq_band.hip -- host side of the banded direct back-end (C ABI: include/fpsq.h, "band" section): the symbolic phase
 // (ordering, two elimination chains), the block-banded factorisation and the solves, the device-resident eq-QP model
-// (fpsq_band_qp_*), the model with nonlinear constraints (fpsq_band_nlp_*: fpsq_band_nlp.hip.h; with coupling terms:
-// fpsq_band_cnlp.hip.h) and the block entries.
+// (fpsq_band_qp_*), the model with nonlinear constraints, separable or with coupling terms (fpsq_band_nlp_*:
+// fpsq_band_nlp.hip.h) and the block entries.
 #include "fpsq_band.hip.h"
 #include "fpsq_qcsr.h"
 
@@ -1763,9 +1763,8 @@ int fpsq_band_jac_mul(fpsq_band b, int32_t trans, double alpha, const double* x,
 }
 }  // extern "C"
 
-// ------------------- nonlinear (separable-quadratic) equality constraints on the banded handle: kernels and fpsq_band_nlp_*
+// ------- nonlinear (quadratic, separable or coupled) equality constraints on the banded handle: kernels and fpsq_band_nlp_*
 #include "fpsq_band_nlp.hip.h"
-#include "fpsq_band_cnlp.hip.h"  // coupling terms w x_j x_k on that model
 
 // ------------------------------------------- block entries: a (k, n) block of vectors per call, 8 vectors per pass of the factor
 

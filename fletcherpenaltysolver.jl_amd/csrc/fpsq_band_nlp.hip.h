@@ -5,9 +5,25 @@
 // ghjvprod(x, g, v) = H (g .* v): everything nonlinear is a product with the pattern the handle holds and a second value
 // array.  The kernels follow k_bq_* (fpsq_band.hip.h): a lane group per row, grid-stride tiles, sums in a fixed order
 // (lanes by xor shuffles, waves and workgroups in index order), no floating-point atomics.
+//
+// COUPLING TERMS (fpsq_band_nlp_create_coupled) add sum_{t in i} w_t x_jt x_kt to c_i, jt != kt both columns of row i of A, so
+// J(x)_ij = A_ij + H_ij x_j + sum w_t x_partner keeps the handle's pattern, sum_i y_i Hess c_i = diag(H'y) + Wo(y) with Wo(y)
+// sparse symmetric on a pattern S fixed at create, and ghjvprod gains w_t (g_j v_k + g_k v_j).  The index lists come from
+// fpsq_coupled.h.  The model's `lin` view carries S and -Wo(ys) as the R of a sparse objective Hessian, so hprod Val(2) is
+// bq_launches' sparse form with Q = diag(qe) - Wo(ys), unchanged.  It is ONE model: the kernels that walk a row of A or of A'
+// take the terms as the compile-time flag CP (one row walk, `if constexpr` where an expression differs), the kernels on the
+// lists and on S (k_bcn_*) have no separable counterpart, and the drivers branch only where a launch differs.
 #pragma once
+#include "fpsq_coupled.h"
 
 namespace fpsq {
+
+// the partner lists of the entries of one CSR (fpsq_coupled.h): entry k meets x[col[u]] with weight w[u], u in
+// [ptr[k], ptr[k + 1]).  What only the CP forms of the row kernels read; all null on a model without terms.
+struct bn_partners {
+  const int32_t *ptr, *col;
+  const double* w;
+};
 
 // vals[k] = a[k] + h[k] x[colind[k]] over the stored CSR: J(x) where k_band_form_t and the A products read it
 __global__ __launch_bounds__(256) void k_bn_vals(const double* __restrict__ a, const double* __restrict__ h,
@@ -35,12 +51,29 @@ __global__ __launch_bounds__(256) void k_bn_tvals(const int32_t* __restrict__ t_
   }
 }
 
-// The prologue of an objgrad: one pass over the stored CSR reading J (vals), h and the packed pair xg[c] = {g_c, x_c}
-// (k_bq_pack<false>): c_p = sum (J - 1/2 h x_c) x_c - b_p, r[p] = {(J g)_p, -c_p} where the sweeps read it (zero on the
-// padding), keep[p] = c_p; part[2 blk] = this workgroup's slice of f = x.(1/2 q x + d), part[2 blk + 1] = of c.c
-template <int LG>
+// With coupling terms: vals[k] = a[k] + h[k] x[col[k]] + sum_u pw[u] x[pcol[u]] over the entries of ONE CSR and their partner
+// lists: launched on the stored structure (col = colind) and on the transposed one (col = the entry's own column, its lists in
+// the same order), so both value arrays get the same bits
+__global__ __launch_bounds__(256) void k_bcn_vals(const double* __restrict__ a, const double* __restrict__ h,
+                                                  const int32_t* __restrict__ col, const int32_t* __restrict__ pptr,
+                                                  const int32_t* __restrict__ pcol, const double* __restrict__ pw,
+                                                  const double* __restrict__ x, double* __restrict__ vals, int64_t nnz) {
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < nnz; k += (int64_t)gridDim.x * 256) {
+    double s = a[k] + h[k] * x[col[k]];
+    const int e = pptr[k + 1];
+    for (int u = pptr[k]; u < e; ++u) s += pw[u] * x[pcol[u]];
+    vals[k] = s;
+  }
+}
+
+// The prologue of an objgrad: one pass over the stored CSR reading J (vals), a second value array and the packed pair
+// xg[c] = {g_c, x_c} (k_bq_pack<false>): r[p] = {(J g)_p, -c_p} where the sweeps read it (zero on the padding), keep[p] = c_p;
+// part[2 blk] = this workgroup's slice of f = x.(1/2 q x + d), part[2 blk + 1] = of c.c.  Separable: ha = h and
+// c_p = sum (J - 1/2 h x_c) x_c - b_p.  CP: ha = a and c_p = sum 1/2 (J + a) x_c - b_p, which holds for a symmetric curvature of
+// any kind and needs no walk of the term lists (J = vals already holds them).
+template <int LG, bool CP>
 __global__ __launch_bounds__(256) void k_bn_prologue(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
-                                                     const double* __restrict__ vals, const double* __restrict__ h,
+                                                     const double* __restrict__ vals, const double* __restrict__ ha,
                                                      const double* __restrict__ xg, const double* __restrict__ x,
                                                      const double* __restrict__ q, const double* __restrict__ d,
                                                      const double* __restrict__ bp, double* __restrict__ r,
@@ -57,10 +90,13 @@ __global__ __launch_bounds__(256) void k_bn_prologue(const int32_t* __restrict__
     if (p < m) {
       const int e = rowptr[p + 1];
       for (int k = rowptr[p] + l; k < e; k += LG) {
-        const double jv = vals[k], hv = h[k];
+        const double jv = vals[k], hv = ha[k], av = hv;  // (the one array under the name each form knows it by)
         const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)colind[k] * 2);
         a0 += jv * t.x;
-        a1 += (jv - 0.5 * hv * t.y) * t.y;
+        if constexpr (CP)
+          a1 += (0.5 * (jv + av)) * t.y;
+        else
+          a1 += (jv - 0.5 * hv * t.y) * t.y;
       }
     }
 #pragma unroll
@@ -93,12 +129,16 @@ __global__ __launch_bounds__(256) void k_bn_prologue(const int32_t* __restrict__
 }
 
 // c(x) alone, from the model's own arrays (no factorisation has to have put J into the handle), in the caller's row order
-// (rperm: stored row -> the caller's, null = identity): c_p = sum (a + 1/2 h x_c) x_c - b_p
-template <int LG>
+// (rperm: stored row -> the caller's, null = identity): c_p = sum (a + 1/2 h x_c) x_c - b_p; CP:
+// c_p = sum (a + 1/2 h x_c + 1/2 sum_u w x_partner) x_c - b_p (every term is met at both of its entries, half each)
+template <int LG, bool CP>
 __global__ __launch_bounds__(256) void k_bn_cons(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                                                  const double* __restrict__ a, const double* __restrict__ h,
                                                  const double* __restrict__ x, const double* __restrict__ bp,
-                                                 const int32_t* __restrict__ rperm, double* __restrict__ c, int m) {
+                                                 const int32_t* __restrict__ rperm, double* __restrict__ c, int m,
+                                                 bn_partners pt) {
+  [[maybe_unused]] const int32_t *__restrict__ pptr = pt.ptr, *__restrict__ pcol = pt.col;
+  [[maybe_unused]] const double* __restrict__ pw = pt.w;
   constexpr int RPB = 256 / LG;
   const int g = threadIdx.x / LG, l = threadIdx.x % LG;
   const int ntiles = (m + RPB - 1) / RPB;
@@ -109,7 +149,14 @@ __global__ __launch_bounds__(256) void k_bn_cons(const int32_t* __restrict__ row
       const int e = rowptr[p + 1];
       for (int k = rowptr[p] + l; k < e; k += LG) {
         const double xv = x[colind[k]];
-        s += (a[k] + 0.5 * h[k] * xv) * xv;
+        if constexpr (CP) {
+          double ps = 0.0;
+          const int ue = pptr[k + 1];
+          for (int u = pptr[k]; u < ue; ++u) ps += pw[u] * x[pcol[u]];
+          s += (a[k] + 0.5 * h[k] * xv + 0.5 * ps) * xv;
+        } else {
+          s += (a[k] + 0.5 * h[k] * xv) * xv;
+        }
       }
     }
 #pragma unroll
@@ -125,7 +172,8 @@ __global__ __launch_bounds__(256) void k_bn_cons(const int32_t* __restrict__ row
 //   gx_j = gs_j - qe_j p2_j + sigma p2_j + h2 gs_j + rho s3 + eta (x_j - xk_j)       (the gradient in the -ys form)
 // qe, hc, gsm (the model's own copies, what fpsq_band_nlp_hprod runs on) are always written; out, gs, ys, xk may be null.
 // ys and the partials part[2 blk] = slice of c.ys, part[2 blk + 1] = of |x - xk|^2 as in k_bq_epilogue.
-template <int LG>
+// CP also leaves p2_j in tv: its gx_j lacks Wo(ys) p2 + Wo(q2) gs, whose rows need every p2 and gs (k_bcn_finish adds them).
+template <int LG, bool CP>
 __global__ __launch_bounds__(256) void k_bn_epilogue(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
                                                      const double* __restrict__ t_vals, const double* __restrict__ th,
                                                      const double* __restrict__ y, const double* __restrict__ keep,
@@ -134,7 +182,7 @@ __global__ __launch_bounds__(256) void k_bn_epilogue(const int32_t* __restrict__
                                                      const double* __restrict__ d, double sigma, double rho, double eta,
                                                      double* __restrict__ out, double* __restrict__ gs, double* __restrict__ ys,
                                                      double* __restrict__ qe, double* __restrict__ hc, double* __restrict__ gsm,
-                                                     double* __restrict__ part, int n, int m) {
+                                                     double* __restrict__ tv, double* __restrict__ part, int n, int m) {
   constexpr int RPB = 256 / LG;
   __shared__ double sh[8];
   const int g = threadIdx.x / LG, l = threadIdx.x % LG;
@@ -175,6 +223,7 @@ __global__ __launch_bounds__(256) void k_bn_epilogue(const int32_t* __restrict__
       qe[j] = qev;
       hc[j] = h3;
       gsm[j] = gsv;
+      if constexpr (CP) tv[j] = p2;
       if (gs) gs[j] = gsv;
       if (out) out[j] = gsv + (sigma - qev) * p2 + h2 * gsv + rho * s3 + eta * dx;
       red[1] += dx * dx;
@@ -195,6 +244,55 @@ __global__ __launch_bounds__(256) void k_bn_epilogue(const int32_t* __restrict__
   }
 }
 
+// With coupling terms, behind the epilogue: the values of -Wo(ys), Wo(q2), Wo(c) on S in one pass over the contributor lists
+// (increasing stored row): y[p] = {q1, q2} the sweeps' solution, keep = c, ys_p = q1 + sigma q2 as the epilogue forms it.
+// rv = -Wo(ys) is the R of the model's `lin` view.
+__global__ __launch_bounds__(256) void k_bcn_assemble(const int32_t* __restrict__ cptr, const int32_t* __restrict__ crow,
+                                                      const double* __restrict__ cw, const double* __restrict__ y,
+                                                      const double* __restrict__ keep, double sigma, double* __restrict__ rv,
+                                                      double* __restrict__ wq2, double* __restrict__ wc, int64_t snz) {
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < snz; k += (int64_t)gridDim.x * 256) {
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    const int e = cptr[k + 1];
+    for (int u = cptr[k]; u < e; ++u) {
+      const int p = crow[u];
+      const double w = cw[u];
+      const f64x2 t = *reinterpret_cast<const f64x2*>(y + (size_t)p * 2);
+      s1 += w * (t.x + sigma * t.y);
+      s2 += w * t.y;
+      s3 += w * keep[p];
+    }
+    rv[k] = -s1;
+    wq2[k] = s2;
+    wc[k] = s3;
+  }
+}
+
+// gx_j += sum_k (Wo(q2)_jk gs_k + Wo(ys)_jk p2_k) over row j of S, a lane group per row
+template <int LG>
+__global__ __launch_bounds__(256) void k_bcn_finish(const int32_t* __restrict__ srp, const int32_t* __restrict__ sci,
+                                                    const double* __restrict__ rv, const double* __restrict__ wq2,
+                                                    const double* __restrict__ p2, const double* __restrict__ gsm,
+                                                    double* __restrict__ out, int n) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s = 0.0;
+    if (j < n) {
+      const int e = srp[j + 1];
+      for (int k = srp[j] + l; k < e; k += LG) {
+        const int c = sci[k];
+        s += wq2[k] * gsm[c] - rv[k] * p2[c];
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (l == 0 && j < n) out[j] += s;
+  }
+}
+
 // hprod Val(2), behind the unchanged k_bq_epilogue<LG, true> (q = qe): Hv += hc .* v   (:560-562: Hcv is not scaled by rho)
 __global__ __launch_bounds__(256) void k_bn_hcv(const double* __restrict__ hc, const double* __restrict__ v,
                                                 double* __restrict__ Hv, int n) {
@@ -202,16 +300,41 @@ __global__ __launch_bounds__(256) void k_bn_hcv(const double* __restrict__ hc, c
   if (j < n) Hv[j] += hc[j] * v[j];
 }
 
+// The same with coupling terms, behind bq_launches' sparse form (Q = diag(qe) - Wo(ys)): Hv_j += hc_j v_j + (Wo(c) v)_j
+template <int LG>
+__global__ __launch_bounds__(256) void k_bcn_hcv(const int32_t* __restrict__ srp, const int32_t* __restrict__ sci,
+                                                 const double* __restrict__ wc, const double* __restrict__ hc,
+                                                 const double* __restrict__ v, double* __restrict__ Hv, int n) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s = 0.0;
+    if (j < n) {
+      const int e = srp[j + 1];
+      for (int k = srp[j] + l; k < e; k += LG) s += wc[k] * v[sci[k]];
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (l == 0 && j < n) Hv[j] += hc[j] * v[j] + s;
+  }
+}
+
 // The epilogue of an hprod Val(1) (:572-634): the hprod rows of k_bq_epilogue with q = qe -- y[p] = {q1, q2} the solutions
 // for {J v, J (qe v)}, keep = J v; s1 = (J'q1)_j = Ptv_j, s2 = (J'q2)_j, s3 = (J'J v)_j -- and a fourth sum h1 = (H'q1)_j:
 //   Hv_j = (qe_j v_j - s2) - qe_j s1 + 2 sigma s1 + rho (s3 + hc_j v_j) + eta v_j - h1 gs_j        (:612-614, :626)
-template <int LG>
+// CP has E = diag(qe) - Wo(ys) in the place of qe: vx is not v but the packed pair xg[j] = {v_j, (E v)_j} of k_bq_pack_sq<HP>
+// (the second solve's right-hand side was J (E v)), (E v)_j stands where qe_j v_j does, and Ptv_j = s1 is left in tv for
+// k_bcn_finish_h1.
+template <int LG, bool CP>
 __global__ __launch_bounds__(256) void k_bn_epilogue_h1(const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_colind,
                                                         const double* __restrict__ t_vals, const double* __restrict__ th,
                                                         const double* __restrict__ y, const double* __restrict__ keep,
-                                                        const double* __restrict__ v, const double* __restrict__ qe,
+                                                        const double* __restrict__ vx, const double* __restrict__ qe,
                                                         const double* __restrict__ hc, const double* __restrict__ gsm,
-                                                        double sigma, double rho, double eta, double* __restrict__ out, int n) {
+                                                        double sigma, double rho, double eta, double* __restrict__ out,
+                                                        double* __restrict__ tv, int n) {
   constexpr int RPB = 256 / LG;
   const int g = threadIdx.x / LG, l = threadIdx.x % LG;
   const int ntiles = (n + RPB - 1) / RPB;
@@ -238,18 +361,61 @@ __global__ __launch_bounds__(256) void k_bn_epilogue_h1(const int32_t* __restric
       h1 += __shfl_xor(h1, o);
     }
     if (l == 0 && j < n) {
-      const double vv = v[j], qv = qe[j];
-      out[j] = (qv * vv - s2) - qv * s1 + 2.0 * sigma * s1 + rho * (s3 + hc[j] * vv) + eta * vv - h1 * gsm[j];
+      if constexpr (CP) {
+        const f64x2 t = *reinterpret_cast<const f64x2*>(vx + (size_t)j * 2);
+        const double vv = t.x, qv = qe[j];
+        out[j] = (t.y - s2) - qv * s1 + 2.0 * sigma * s1 + rho * (s3 + hc[j] * vv) + eta * vv - h1 * gsm[j];
+        tv[j] = s1;
+      } else {
+        const double vv = vx[j], qv = qe[j];
+        out[j] = (qv * vv - s2) - qv * s1 + 2.0 * sigma * s1 + rho * (s3 + hc[j] * vv) + eta * vv - h1 * gsm[j];
+      }
     }
   }
 }
 
-// Ssv = ghjvprod(x, gs, v) = H (gs .* v) (:600) over the stored CSR, straight into the sweeps' right-hand-side layout:
-// r[p] = {Ssv_p, 0}, zero on the padding
+// hprod Val(1) with coupling terms, the rows of S: Hv_j += sum_k (Wo(ys)_jk Ptv_k + rho Wo(c)_jk v_k - Wo(q1)_jk gs_k).  Wo(q1)
+// is used once, so its entries are summed here from the contributor lists and the first solve's y[p] = {q1, .} (before the
+// second solve takes y)
 template <int LG>
+__global__ __launch_bounds__(256) void k_bcn_finish_h1(const int32_t* __restrict__ srp, const int32_t* __restrict__ sci,
+                                                       const int32_t* __restrict__ cptr, const int32_t* __restrict__ crow,
+                                                       const double* __restrict__ cw, const double* __restrict__ rv,
+                                                       const double* __restrict__ wc, const double* __restrict__ y,
+                                                       const double* __restrict__ tv, const double* __restrict__ v,
+                                                       const double* __restrict__ gsm, double rho, double* __restrict__ out,
+                                                       int n) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    double s = 0.0;
+    if (j < n) {
+      const int e = srp[j + 1];
+      for (int k = srp[j] + l; k < e; k += LG) {
+        const int c = sci[k];
+        double wq1 = 0.0;
+        const int ue = cptr[k + 1];
+        for (int u = cptr[k]; u < ue; ++u) wq1 += cw[u] * y[(size_t)crow[u] * 2];
+        s += (rho * wc[k]) * v[c] - rv[k] * tv[c] - wq1 * gsm[c];
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (l == 0 && j < n) out[j] += s;
+  }
+}
+
+// Ssv = ghjvprod(x, gs, v) = H (gs .* v) (:600) over the stored CSR, straight into the sweeps' right-hand-side layout:
+// r[p] = {Ssv_p, 0}, zero on the padding.  CP: with the terms, Ssv_p = sum_k gs_c (h_k v_c + sum_u w v_partner)
+template <int LG, bool CP>
 __global__ __launch_bounds__(256) void k_bn_hgv(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                                                 const double* __restrict__ h, const double* __restrict__ gsm,
-                                                const double* __restrict__ v, double* __restrict__ r, int m, int mpad) {
+                                                const double* __restrict__ v, double* __restrict__ r, int m, int mpad,
+                                                bn_partners pt) {
+  [[maybe_unused]] const int32_t *__restrict__ pptr = pt.ptr, *__restrict__ pcol = pt.col;
+  [[maybe_unused]] const double* __restrict__ pw = pt.w;
   constexpr int RPB = 256 / LG;
   const int g = threadIdx.x / LG, l = threadIdx.x % LG;
   const int ntiles = (mpad + RPB - 1) / RPB;
@@ -260,7 +426,14 @@ __global__ __launch_bounds__(256) void k_bn_hgv(const int32_t* __restrict__ rowp
       const int e = rowptr[p + 1];
       for (int k = rowptr[p] + l; k < e; k += LG) {
         const int c = colind[k];
-        s += h[k] * (gsm[c] * v[c]);
+        if constexpr (CP) {
+          double t = h[k] * v[c];
+          const int ue = pptr[k + 1];
+          for (int u = pptr[k]; u < ue; ++u) t += pw[u] * v[pcol[u]];
+          s += gsm[c] * t;
+        } else {
+          s += h[k] * (gsm[c] * v[c]);
+        }
       }
     }
 #pragma unroll
@@ -391,11 +564,11 @@ __global__ __launch_bounds__(256) void k_bn_lc_epilogue_h1(const int32_t* __rest
 
 // ---- host side
 
-// What a model with coupling terms (fpsq_band_nlp_create_coupled, fpsq_band_cnlp.hip.h) holds besides fpsq_band_nlp_s' own arrays:
-// the lists of fpsq_coupled.h on the device -- partner lists of the stored and of the transposed entries, the latter's own
-// columns, the contributor lists of S -- and the values of Wo(q2), Wo(c) on S.  S itself, -Wo(ys) and the n-vector tv (p2 resp.
-// Ptv) are the `lin` view's r_rowptr / r_colind / r_vals / tv.  The buffers are on the model's list.
-struct fpsq_band_cnlp_s {
+// What a model with coupling terms (fpsq_band_nlp_create_coupled) holds besides fpsq_band_nlp_s' own arrays: the lists of
+// fpsq_coupled.h on the device -- partner lists of the stored and of the transposed entries, the latter's own columns, the
+// contributor lists of S -- and the values of Wo(q2), Wo(c) on S.  S itself, -Wo(ys) and the n-vector tv (p2 resp. Ptv) are the
+// `lin` view's r_rowptr / r_colind / r_vals / tv.  The buffers are on the model's list.
+struct bn_terms_s {
   int32_t *pptr = nullptr, *pcol = nullptr, *tpptr = nullptr, *tpcol = nullptr, *tcol = nullptr;
   double *pw = nullptr, *tpw = nullptr;
   int32_t *cptr = nullptr, *crow = nullptr;
@@ -409,7 +582,8 @@ struct fpsq_band_cnlp_s {
 // fpsq_band_qp_s does.
 struct fpsq_band_nlp_s {
   fpsq_band b = nullptr;
-  fpsq_band_cnlp_s* cp = nullptr;  // non-null: the model has coupling terms and runs fpsq_band_cnlp.hip.h's launches
+  bool coupled = false;  // the model has coupling terms: `cp` is filled and the launches take their CP forms
+  bn_terms_s cp;
   double *q = nullptr, *d = nullptr, *bp = nullptr;  // n, n, m (b in the STORED row order)
   double *a = nullptr, *h = nullptr, *ta = nullptr, *th = nullptr;  // nnz (+ the virtual entries' slot), t_nnz
   double *qe = nullptr, *hc = nullptr, *gs = nullptr;               // q - H'ys, H'c, gs of the last successful objgrad
@@ -425,7 +599,6 @@ extern "C" {
 int fpsq_band_nlp_destroy(fpsq_band_nlp nlp) {
   if (!nlp) return FPSQ_ERR_ARG;
   for (void* p : nlp->allocs) hipFree(p);
-  delete nlp->cp;
   delete nlp;
   return FPSQ_OK;
 }
@@ -433,14 +606,26 @@ int fpsq_band_nlp_destroy(fpsq_band_nlp nlp) {
 }  // extern "C"
 
 namespace {
-const char kNlpCooRefused[] =
-    "the handle was created by a fpsq_band_create_coo entry (its callers do not know the slot order)";
+// the grid of a kernel that gives a thread an entry (k_bn_vals, k_bcn_vals, k_bcn_assemble, k_gather_d): 256 entries a
+// workgroup, capped; above the cap a workgroup walks on
+dim3 flat_grid(int64_t len) { return dim3((unsigned)std::max<int64_t>(std::min<int64_t>((len + 255) / 256, 4096), 1)); }
 
-// What the two create entries share, behind their checks of the handle's kind.  With long columns the transposed arrays span
-// t_nnz entries and gather a slot behind the stored values (a = 1, h = 0) into the virtual ones; without them t_nnz = nnz and
-// every size, lane group and launch is what it was before the handle's kind was looked at.
-int band_nlp_make(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
-                  const double* h_vals, fpsq_band_nlp* out) {
+// What the three create entries share: their checks (`entry` names the caller in a refusal; `arrow`: border rows and long
+// columns are taken) and the model.  With long columns the transposed arrays span t_nnz entries and gather a slot behind the
+// stored values (a = 1, h = 0) into the virtual ones; without them t_nnz = nnz and every size, lane group and launch is what
+// it was before the handle's kind was looked at.
+int band_nlp_make(const char* entry, bool arrow, fpsq_band b, const double* qdiag, const double* d, const double* bvec,
+                  const double* a_vals, const double* h_vals, fpsq_band_nlp* out) {
+  if (!b || !qdiag || !d || !bvec || !out || (b->nnz > 0 && (!a_vals || !h_vals))) return FPSQ_ERR_ARG;
+  const char* why =
+      !arrow && b->border > 0 ? "the handle has border rows"
+      : !arrow && b->cols > 0 ? "the handle has long columns (they change the transposed structure)"
+      : b->coo_nnz >= 0       ? "the handle was created by a fpsq_band_create_coo entry (its callers do not know the slot order)"
+                              : nullptr;
+  if (why) {
+    b->err = std::string(entry) + ": " + why;
+    return FPSQ_ERR_STATE;
+  }
   hipSetDevice(b->device);
   if (!b->scal) {  // the scalars of a call: device side and pinned host side
     if (dalloc(b, &b->scal, 8)) return FPSQ_ERR_HIP;
@@ -483,8 +668,7 @@ int band_nlp_make(fpsq_band b, const double* qdiag, const double* d, const doubl
   lin.partE = nlp->partE;
   // the two value arrays into both orders, by the gathers a factorisation uses for its values
   hipStream_t s = b->stream;
-  const dim3 gz((unsigned)std::min<int64_t>((b->nnz + 255) / 256, 4096));
-  const dim3 gt((unsigned)std::min<int64_t>((b->t_nnz + 255) / 256, 4096));
+  const dim3 gz = flat_grid(b->nnz), gt = flat_grid(b->t_nnz);
   for (int w = 0; w < 2 && b->nnz > 0; ++w) {
     const double* src = w ? h_vals : a_vals;
     double *st = w ? nlp->h : nlp->a, *tr = w ? nlp->th : nlp->ta;
@@ -514,51 +698,104 @@ int band_nlp_make(fpsq_band b, const double* qdiag, const double* d, const doubl
   return FPSQ_OK;
 }
 
-// a model with coupling terms (nlp->cp): fpsq_band_cnlp.hip.h
-int band_cnlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* c);
-int band_cnlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, double sigma, double rho, double eta, double delta,
-                      const double* xk, double* fx, double* gx, double* ys, double* gs, int32_t* info);
-void band_cnlp_hprod_launches(fpsq_band b, fpsq_band_nlp nlp, const double* v, double sigma, double rho, double eta,
-                              int32_t hessian_approx, double* Hv);
+// The term lists of a model that band_nlp_make has made (fpsq_coupled.h builds them on the host from the handle's structure)
+int band_nlp_attach(fpsq_band b, fpsq_band_nlp nlp, int64_t nterms, const int32_t* t_row, const int32_t* t_j, const int32_t* t_k,
+                    const double* t_w) {
+  const size_t T = (size_t)nterms, nnz = (size_t)b->nnz, tnz = (size_t)b->t_nnz, n = (size_t)b->n, m = (size_t)b->m;
+  std::vector<int32_t> row(T), cj(T), ck(T), rp(m + 1), ci(std::max<size_t>(nnz, 1)), tperm(std::max<size_t>(tnz, 1));
+  std::vector<double> w(T);
+  CHK(b, hipMemcpy(row.data(), t_row, T * 4, hipMemcpyDefault));
+  CHK(b, hipMemcpy(cj.data(), t_j, T * 4, hipMemcpyDefault));
+  CHK(b, hipMemcpy(ck.data(), t_k, T * 4, hipMemcpyDefault));
+  CHK(b, hipMemcpy(w.data(), t_w, T * 8, hipMemcpyDefault));
+  CHK(b, hipMemcpy(rp.data(), b->rowptr, (m + 1) * 4, hipMemcpyDeviceToHost));
+  if (nnz) CHK(b, hipMemcpy(ci.data(), b->colind, nnz * 4, hipMemcpyDeviceToHost));
+  if (tnz) CHK(b, hipMemcpy(tperm.data(), b->t_perm, tnz * 4, hipMemcpyDeviceToHost));
+  std::vector<int32_t> rinv;
+  if (b->reordered) {
+    rinv.resize(m);
+    for (size_t p = 0; p < m; ++p) rinv[b->rperm_host[p]] = (int32_t)p;
+  }
+  CoupledLists L;
+  const std::string what = coupled_build((int64_t)n, (int64_t)m, rp.data(), ci.data(), b->reordered ? rinv.data() : nullptr,
+                                         (int64_t)tnz, tperm.data(), nterms, row.data(), cj.data(), ck.data(), w.data(), L);
+  if (!what.empty()) {
+    b->err = "band_nlp_create_coupled: " + what;
+    return FPSQ_ERR_ARG;
+  }
+  bn_terms_s* cp = &nlp->cp;
+  nlp->coupled = true;
+  fpsq_band_qp_s& lin = nlp->lin;
+  const size_t snz = L.sci.size(), s4 = std::max<size_t>(snz, 1) * 4, s8 = std::max<size_t>(snz, 1) * 8;
+  cp->snz = (int64_t)snz;
+  lin.sparse_q = true;
+  lin.lgR = lane_group((int64_t)snz, (int64_t)n);
+  lin.gridR = bq_grid((int64_t)n, lin.lgR);
+  const auto H2D = hipMemcpyHostToDevice;
+  if (!qp_buffers(nlp, {{(void**)&cp->pptr, (nnz + 1) * 4, L.pptr.data(), H2D},
+                        {(void**)&cp->pcol, 2 * T * 4, L.pcol.data(), H2D},
+                        {(void**)&cp->pw, 2 * T * 8, L.pw.data(), H2D},
+                        {(void**)&cp->tpptr, (tnz + 1) * 4, L.tpptr.data(), H2D},
+                        {(void**)&cp->tpcol, 2 * T * 4, L.tpcol.data(), H2D},
+                        {(void**)&cp->tpw, 2 * T * 8, L.tpw.data(), H2D},
+                        {(void**)&cp->tcol, std::max<size_t>(tnz, 1) * 4, tnz ? L.tcol.data() : nullptr, H2D},
+                        {(void**)&lin.r_rowptr, (n + 1) * 4, L.srp.data(), H2D},
+                        {(void**)&lin.r_colind, s4, L.sci.data(), H2D},
+                        {(void**)&cp->cptr, (snz + 1) * 4, L.cptr.data(), H2D},
+                        {(void**)&cp->crow, 2 * T * 4, L.crow.data(), H2D},
+                        {(void**)&cp->cw, 2 * T * 8, L.cw.data(), H2D},
+                        {(void**)&lin.r_vals, s8, nullptr, H2D},
+                        {(void**)&cp->wq2, s8, nullptr, H2D},
+                        {(void**)&cp->wc, s8, nullptr, H2D},
+                        {(void**)&lin.tv, n * 8, nullptr, H2D},
+                        {(void**)&lin.partF, (size_t)lin.gridR * 8, nullptr, H2D}})) {
+    b->err = "band_nlp_create_coupled: cannot allocate or fill the term lists";
+    return FPSQ_ERR_HIP;
+  }
+  return FPSQ_OK;
+}
 }  // namespace
 
 extern "C" {
 
 int fpsq_band_nlp_create(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
                          const double* h_vals, fpsq_band_nlp* out) {
-  if (!b || !qdiag || !d || !bvec || !out || (b->nnz > 0 && (!a_vals || !h_vals))) return FPSQ_ERR_ARG;
-  const char* why = b->border > 0    ? "the handle has border rows"
-                    : b->cols > 0    ? "the handle has long columns (they change the transposed structure)"
-                    : b->coo_nnz >= 0 ? kNlpCooRefused
-                                      : nullptr;
-  if (why) {
-    b->err = std::string("band_nlp_create: ") + why;
-    return FPSQ_ERR_STATE;
-  }
-  return band_nlp_make(b, qdiag, d, bvec, a_vals, h_vals, out);
+  return band_nlp_make("band_nlp_create", false, b, qdiag, d, bvec, a_vals, h_vals, out);
 }
 
 int fpsq_band_nlp_create_arrow(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
                                const double* h_vals, fpsq_band_nlp* out) {
-  if (!b || !qdiag || !d || !bvec || !out || (b->nnz > 0 && (!a_vals || !h_vals))) return FPSQ_ERR_ARG;
-  if (b->coo_nnz >= 0) {
-    b->err = std::string("band_nlp_create_arrow: ") + kNlpCooRefused;
-    return FPSQ_ERR_STATE;
+  return band_nlp_make("band_nlp_create_arrow", true, b, qdiag, d, bvec, a_vals, h_vals, out);
+}
+
+int fpsq_band_nlp_create_coupled(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
+                                 const double* h_vals, int64_t nterms, const int32_t* t_row, const int32_t* t_j,
+                                 const int32_t* t_k, const double* t_w, fpsq_band_nlp* out) {
+  if (nterms < 0 || (nterms > 0 && (!t_row || !t_j || !t_k || !t_w))) return FPSQ_ERR_ARG;
+  fpsq_band_nlp nlp = nullptr;
+  if (int rc = band_nlp_make("band_nlp_create_coupled", false, b, qdiag, d, bvec, a_vals, h_vals, &nlp)) return rc;
+  if (nterms > 0) {  // (without terms the model IS fpsq_band_nlp_create's: the same launches, the same bits)
+    if (int rc = band_nlp_attach(b, nlp, nterms, t_row, t_j, t_k, t_w)) {
+      fpsq_band_nlp_destroy(nlp);
+      return rc;
+    }
   }
-  return band_nlp_make(b, qdiag, d, bvec, a_vals, h_vals, out);
+  *out = nlp;
+  return FPSQ_OK;
 }
 
 int fpsq_band_nlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* c) {
   if (!b || !nlp || nlp->b != b || !x || !c) return FPSQ_ERR_ARG;
-  if (nlp->cp) return band_cnlp_cons(b, nlp, x, c);
   hipSetDevice(b->device);
   if (int rc = wait_input(b)) return rc;
   const StagedArg ax = staged(b, x, b->in_a, (size_t)b->n);
   if (int rc = stage_in(b, ax)) return rc;
   const StagedArg oc = staged(b, c, b->o_q1, (size_t)b->m);
   const int lg = nlp->lin.lgA;
-  WITH_LANE_GROUP(lg, hipLaunchKernelGGL(k_bn_cons<LG>, dim3(bq_grid(b->m, lg)), dim3(256), 0, b->stream, b->rowptr, b->colind,
-                                         nlp->a, nlp->h, ax.tile(), nlp->bp, b->row_perm(), oc.tile(), (int)b->m))
+  const bn_partners pt{nlp->cp.pptr, nlp->cp.pcol, nlp->cp.pw};
+  WITH_LANE_GROUP(lg, WITH_BOOL(nlp->coupled, CP, hipLaunchKernelGGL(
+      (k_bn_cons<LG, CP>), dim3(bq_grid(b->m, lg)), dim3(256), 0, b->stream, b->rowptr, b->colind, nlp->a, nlp->h, ax.tile(),
+      nlp->bp, b->row_perm(), oc.tile(), (int)b->m, pt)))
   if (int rc = stage_back(b, oc)) return rc;
   CHK(b, hipStreamSynchronize(b->stream));
   return FPSQ_OK;
@@ -567,10 +804,11 @@ int fpsq_band_nlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* 
 int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, double sigma, double rho, double eta, double delta,
                           const double* xk, double* fx, double* gx, double* ys, double* gs, int32_t* info) {
   if (!b || !nlp || nlp->b != b || !x || !fx || !(delta >= 0.0)) return FPSQ_ERR_ARG;
-  if (nlp->cp) return band_cnlp_objgrad(b, nlp, x, sigma, rho, eta, delta, xk, fx, gx, ys, gs, info);
   hipSetDevice(b->device);
   hipStream_t s = b->stream;
   const fpsq_band_qp_s& lin = nlp->lin;
+  const bn_terms_s& cp = nlp->cp;
+  const bool coupled = nlp->coupled;
   const int n = (int)b->n, m = (int)b->m, mpad = (int)b->mpad;
   nlp->evaluated = false;
   b->factored = false;
@@ -581,16 +819,19 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
   if (int rc = stage_in(b, ax)) return rc;
   const StagedArg axk = staged(b, eta > 0.0 ? xk : nullptr, b->in_b, (size_t)n);
   if (int rc = stage_in(b, axk)) return rc;
-  // 1: J(x) into the handle's value arrays, the stored CSR and the transposed one
+  // 1: J(x) into the handle's value arrays, the stored CSR and the transposed one (with terms: by the same kernel)
   b->have_vals = true;
-  if (b->nnz > 0) {
-    hipLaunchKernelGGL(k_bn_vals, dim3((unsigned)std::min<int64_t>((b->nnz + 255) / 256, 4096)), dim3(256), 0, s, nlp->a, nlp->h,
-                       b->colind, ax.tile(), b->vals, b->nnz);
+  if (b->nnz > 0 && coupled) {
+    hipLaunchKernelGGL(k_bcn_vals, flat_grid(b->nnz), dim3(256), 0, s, nlp->a, nlp->h, b->colind, cp.pptr, cp.pcol, cp.pw,
+                       ax.tile(), b->vals, b->nnz);
+    hipLaunchKernelGGL(k_bcn_vals, flat_grid(b->t_nnz), dim3(256), 0, s, nlp->ta, nlp->th, cp.tcol, cp.tpptr, cp.tpcol, cp.tpw,
+                       ax.tile(), b->t_vals, b->t_nnz);
+  } else if (b->nnz > 0) {
+    hipLaunchKernelGGL(k_bn_vals, flat_grid(b->nnz), dim3(256), 0, s, nlp->a, nlp->h, b->colind, ax.tile(), b->vals, b->nnz);
     WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_tvals<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, nlp->ta, nlp->th,
                                                 ax.tile(), b->t_vals, n))
     if (b->fb_nnz > 0)  // (long columns and k_band_form: the values of the other columns alone, as fpsq_band_factorize)
-      hipLaunchKernelGGL(k_gather_d, dim3((unsigned)std::min<int64_t>((b->fb_nnz + 255) / 256, 4096)), dim3(256), 0, s, b->vals,
-                         b->fb_perm, b->fb_vals, b->fb_nnz);
+      hipLaunchKernelGGL(k_gather_d, flat_grid(b->fb_nnz), dim3(256), 0, s, b->vals, b->fb_perm, b->fb_vals, b->fb_nnz);
   }
   // 2: the numeric factorisation on them
   if (int rc = band_factor_numeric(b, delta, info)) return rc;  // (1: no valid factor, *info says where; nothing is evaluated)
@@ -600,19 +841,26 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
                   oys = staged(b, ys, b->o_q1, (size_t)m);
   double* keep = b->cols ? b->bd_keep : b->o_q2;  // (long columns: the operand has virtual rows, as in bq_launches)
   hipLaunchKernelGGL(k_bq_pack<false>, grid256(n), dim3(256), 0, s, ax.tile(), nlp->q, nlp->d, b->xn, n);
-  WITH_LANE_GROUP(lin.lgA, hipLaunchKernelGGL(k_bn_prologue<LG>, dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals,
-                                              nlp->h, b->xn, ax.tile(), nlp->q, nlp->d, nlp->bp, b->r2, keep, nlp->partP, m, mpad,
-                                              n))
+  WITH_LANE_GROUP(lin.lgA, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
+      (k_bn_prologue<LG, CP>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, CP ? nlp->a : nlp->h, b->xn,
+      ax.tile(), nlp->q, nlp->d, nlp->bp, b->r2, keep, nlp->partP, m, mpad, n)))
   if (b->cols) cols_keep<1>(b, keep);
   band_solve(b);
-  WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_epilogue<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind,
-                                              b->t_vals, nlp->th, b->r2, keep, b->row_perm(), ax.tile(), axk.tile(), nlp->q, nlp->d,
-                                              sigma, rho, eta, ogx.tile(), ogs.tile(), oys.tile(), nlp->qe, nlp->hc, nlp->gs,
-                                              nlp->partE, n, m))
+  WITH_LANE_GROUP(lin.lgT, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
+      (k_bn_epilogue<LG, CP>), dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, nlp->th, b->r2, keep,
+      b->row_perm(), ax.tile(), axk.tile(), nlp->q, nlp->d, sigma, rho, eta, ogx.tile(), ogs.tile(), oys.tile(), nlp->qe, nlp->hc,
+      nlp->gs, lin.tv, nlp->partE, n, m)))
   if (b->cols)  // the curvature sums at the long columns, whose transposed rows are virtual
     hipLaunchKernelGGL(k_bn_lc_epilogue, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->lc_cols, nlp->h,
                        b->r2, keep, ax.tile(), axk.tile(), nlp->q, nlp->gs, sigma, rho, eta, ogx.tile(), nlp->qe, nlp->hc, mpad,
                        b->bc_grid);
+  if (coupled) {  // the values of Wo on S, then the rows of S that gx lacks
+    hipLaunchKernelGGL(k_bcn_assemble, flat_grid(cp.snz), dim3(256), 0, s, cp.cptr, cp.crow, cp.cw, b->r2, keep, sigma,
+                       lin.r_vals, cp.wq2, cp.wc, cp.snz);
+    if (gx)
+      WITH_LANE_GROUP(lin.lgR, hipLaunchKernelGGL(k_bcn_finish<LG>, dim3(lin.gridR), dim3(256), 0, s, lin.r_rowptr, lin.r_colind,
+                                                  lin.r_vals, cp.wq2, lin.tv, nlp->gs, ogx.tile(), n))
+  }
   hipLaunchKernelGGL(k_bq_phi, dim3(1), dim3(256), 0, s, nlp->partP, lin.gridP, nlp->partE, lin.gridE, rho, eta, b->scal);
   for (const StagedArg* o : {&ogx, &ogs, &oys})
     if (int rc = stage_back(b, *o)) return rc;
@@ -641,34 +889,50 @@ int fpsq_band_nlp_hprod(fpsq_band b, fpsq_band_nlp nlp, const double* v, double 
   if (int rc = eval_begin(b)) return rc;
   hipStream_t s = b->stream;
   fpsq_band_qp_s& lin = nlp->lin;
+  const bn_terms_s& cp = nlp->cp;
+  const bool coupled = nlp->coupled;
   const int n = (int)b->n, m = (int)b->m, mpad = (int)b->mpad;
   rho = rho > 0.0 ? rho : 0.0;
   eta = eta > 0.0 ? eta : 0.0;
   const StagedArg av = staged(b, v, b->in_a, (size_t)n);
   if (int rc = stage_in(b, av)) return rc;
   const StagedArg ah = staged(b, Hv, b->o_p1, (size_t)n);
-  if (nlp->cp) {
-    band_cnlp_hprod_launches(b, nlp, av.tile(), sigma, rho, eta, hessian_approx, ah.tile());
-  } else if (hessian_approx == 2) {  // the linear model's launches with q = qe, then the curvature of rho/2 |c|^2
+  if (hessian_approx == 2) {
+    // the linear model's launches with q = qe (with terms: their sparse form, Q = diag(qe) - Wo(ys)), then the curvature of
+    // rho/2 |c|^2
     bq_launches(b, &lin, true, av.tile(), nullptr, sigma, rho, eta, ah.tile(), nullptr, nullptr);
-    if (rho > 0.0) hipLaunchKernelGGL(k_bn_hcv, grid256(n), dim3(256), 0, s, nlp->hc, av.tile(), ah.tile(), n);
+    if (rho > 0.0 && coupled)
+      WITH_LANE_GROUP(lin.lgR, hipLaunchKernelGGL(k_bcn_hcv<LG>, dim3(lin.gridR), dim3(256), 0, s, lin.r_rowptr, lin.r_colind,
+                                                  cp.wc, nlp->hc, av.tile(), ah.tile(), n))
+    else if (rho > 0.0)
+      hipLaunchKernelGGL(k_bn_hcv, grid256(n), dim3(256), 0, s, nlp->hc, av.tile(), ah.tile(), n);
   } else {
     double* keep = b->cols ? b->bd_keep : b->o_q2;
-    hipLaunchKernelGGL(k_bq_pack<true>, grid256(n), dim3(256), 0, s, av.tile(), nlp->qe, nlp->d, b->xn, n);
+    if (coupled)  // xn[j] = {v_j, (E v)_j}, E = diag(qe) - Wo(ys)
+      WITH_LANE_GROUP(lin.lgR, hipLaunchKernelGGL((k_bq_pack_sq<LG, true>), dim3(lin.gridR), dim3(256), 0, s, lin.r_rowptr,
+                                                  lin.r_colind, lin.r_vals, av.tile(), nlp->qe, nlp->d, b->xn, lin.partF, n))
+    else
+      hipLaunchKernelGGL(k_bq_pack<true>, grid256(n), dim3(256), 0, s, av.tile(), nlp->qe, nlp->d, b->xn, n);
     WITH_LANE_GROUP(lin.lgA, hipLaunchKernelGGL((k_bq_prologue<LG, true, false>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr,
                                                 b->colind, b->vals, b->xn, av.tile(), nlp->qe, nlp->d, nlp->bp, b->r2, keep,
                                                 nlp->partP, m, mpad, n))
     if (b->cols) cols_keep<1>(b, keep);
     band_solve(b);
-    WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_epilogue_h1<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind,
-                                                b->t_vals, nlp->th, b->r2, keep, av.tile(), nlp->qe, nlp->hc, nlp->gs, sigma, rho,
-                                                eta, ah.tile(), n))
+    WITH_LANE_GROUP(lin.lgT, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
+        (k_bn_epilogue_h1<LG, CP>), dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, nlp->th, b->r2, keep,
+        CP ? b->xn : av.tile(), nlp->qe, nlp->hc, nlp->gs, sigma, rho, eta, ah.tile(), lin.tv, n)))
     if (b->cols)  // (H'q1)_j at the long columns, before the second solve takes b->r2
       hipLaunchKernelGGL(k_bn_lc_epilogue_h1, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->lc_cols, nlp->h,
                          b->r2, keep, av.tile(), nlp->qe, nlp->hc, nlp->gs, sigma, rho, eta, ah.tile(), mpad, b->bc_grid);
-    // z = M^-1 H (gs .* v) on the cached factor (tau = delta, include/fpsq.h), Hv -= J'z
-    WITH_LANE_GROUP(lin.lgA, hipLaunchKernelGGL(k_bn_hgv<LG>, dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, nlp->h,
-                                                nlp->gs, av.tile(), b->r2, m, mpad))
+    if (coupled)  // the rows of S, while b->r2 still holds the first solve
+      WITH_LANE_GROUP(lin.lgR, hipLaunchKernelGGL(k_bcn_finish_h1<LG>, dim3(lin.gridR), dim3(256), 0, s, lin.r_rowptr,
+                                                  lin.r_colind, cp.cptr, cp.crow, cp.cw, lin.r_vals, cp.wc, b->r2, lin.tv,
+                                                  av.tile(), nlp->gs, rho, ah.tile(), n))
+    // z = M^-1 ghjvprod(x, gs, v) = M^-1 H (gs .* v) [+ the terms] on the cached factor (tau = delta, include/fpsq.h), Hv -= J'z
+    const bn_partners pt{cp.pptr, cp.pcol, cp.pw};
+    WITH_LANE_GROUP(lin.lgA, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
+        (k_bn_hgv<LG, CP>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, nlp->h, nlp->gs, av.tile(), b->r2, m, mpad,
+        pt)))
     band_solve(b);
     WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_jtz<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind,
                                                 b->t_vals, b->r2, ah.tile(), n))

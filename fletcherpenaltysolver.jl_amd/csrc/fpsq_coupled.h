@@ -1,5 +1,5 @@
 // fpsq_coupled.h -- the coupling terms w x_j x_k of fpsq_band_nlp_create_coupled on the host: the checks, and the index lists the
-// k_bcn_* kernels (fpsq_band_cnlp.hip.h) walk.  A term t = (row, j, k, w) adds w x_j x_k to c_row; j and k are both columns of
+// k_bcn_* and the CP forms of the k_bn_* kernels (fpsq_band_nlp.hip.h) walk.  A term t = (row, j, k, w) adds w x_j x_k to c_row; j and k are both columns of
 // that row of the handle's pattern, so J(x) keeps the pattern.  Host-only: needs neither the device runtime nor a handle
 // (tests/coupled_nlp_model.py restates it in numpy).
 //   partner lists   per STORED entry e = (p, c): the pairs (column, w) with J(x)_e = a_e + h_e x_c + sum w x_column, in term order;

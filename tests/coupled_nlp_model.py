@@ -1,7 +1,7 @@
 """The coupled quadratic model in numpy, fp64, assembled THE WAY THE DEVICE ASSEMBLES IT (csrc/fpsq_coupled.h: the index lists;
-csrc/fpsq_band_cnlp.hip.h: the sums of the k_bcn_* kernels and of the launches they share with the other models), on a STORED
-row order of the caller's choice (`rperm`: stored row -> the caller's, what the symbolic phase of a reordered or two-chain
-handle does to the rows; columns keep their order):
+csrc/fpsq_band_nlp.hip.h: the sums of the k_bn_*<LG, true> and k_bcn_* kernels and of the launches they share with the other
+models), on a STORED row order of the caller's choice (`rperm`: stored row -> the caller's, what the symbolic phase of a
+reordered or two-chain handle does to the rows; columns keep their order):
 
   * `build_lists` restates coupled_build: every term is attached to its two stored entries through the row permutation, the
     per-entry partner lists (column, w) in term order, the same lists in the transposed order through t_perm, the pattern S of
@@ -114,7 +114,7 @@ class CoupledNLPModel:
         return sp.csr_matrix((tvals, self.t_ci, self.t_rp), shape=(self.qp.n, self.qp.m))
 
     def cons(self, x):
-        """k_bcn_cons: from the model's own arrays, every term met at both of its entries, half each; the caller's row order"""
+        """k_bn_cons<LG, true>: from the model's own arrays, every term met at both of its entries, half each; the caller's rows"""
         ps = np.array([sum(w * x[c] for c, w in lst) for lst in self.L["partners"]])
         xv = x[self.ci]
         s = np.bincount(self.rows, (self.a + 0.5 * self.h * xv + 0.5 * ps) * xv, self.qp.m) - self.bp
@@ -180,10 +180,10 @@ class CoupledNLPModel:
                 Hv = Hv + (hc * v + self._s_mul(wc, v))                         # k_bcn_hcv
             return Hv
         h1 = self._Jt(self.th) @ q1
-        Hv = (Ev - s2) - qe * s1 + 2.0 * sigma * s1 + rho * (s3 + hc * v) + eta * v - h1 * gs   # k_bcn_epilogue_h1
+        Hv = (Ev - s2) - qe * s1 + 2.0 * sigma * s1 + rho * (s3 + hc * v) + eta * v - h1 * gs   # k_bn_epilogue_h1<LG, true>
         wq1 = self._on_s(q1)
         Hv = Hv + (rho * self._s_mul(wc, v) - self._s_mul(rv, s1) - self._s_mul(wq1, gs))      # k_bcn_finish_h1
         t = self.h * v[self.ci] + np.array([sum(w * v[c] for c, w in lst) for lst in self.L["partners"]])
-        ssv = np.bincount(self.rows, gs[self.ci] * t, self.qp.m)                                # k_bcn_hgv
+        ssv = np.bincount(self.rows, gs[self.ci] * t, self.qp.m)                                # k_bn_hgv<LG, true>
         z = self._msolve(ssv[:, None])[:, 0]
         return Hv - Jt @ z                                                                       # k_bn_jtz

@@ -5,9 +5,9 @@ tests/test_gpu_band_nlp.py holds this back-end to: max|a - b| / max|b| < 1e-9 pe
 Dropping the terms moves the reference gx and Hv by more than 1e-3 on every case (tests/test_band_coupled_nlp_cpu.py), so the
 bar tells the two models apart.  The cases: tests/coupled_cases.py.
 
-Second trips of the grid-stride loops: the case `stride` takes k_bcn_vals (both launches), k_bcn_prologue, k_bcn_epilogue,
-k_bcn_finish, k_bcn_hcv, k_bcn_epilogue_h1, k_bcn_finish_h1, k_bcn_hgv and k_bcn_cons through theirs; k_bcn_assemble's no test
-reaches (coupled_cases.py STRIDE)."""
+Second trips of the grid-stride loops: the case `stride` takes k_bcn_vals (both launches), k_bn_prologue<LG, true>,
+k_bn_epilogue<LG, true>, k_bcn_finish, k_bcn_hcv, k_bn_epilogue_h1<LG, true>, k_bcn_finish_h1, k_bn_hgv<LG, true> and
+k_bn_cons<LG, true> through theirs; k_bcn_assemble's no test reaches (coupled_cases.py STRIDE)."""
 import ctypes as C
 import dataclasses
 import os

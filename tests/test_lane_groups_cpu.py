@@ -58,8 +58,16 @@ def test_the_restated_rule_is_the_one_of_the_header():
     assert [L.lane_group(k, 1) for k in (0, 1, 2, 3, 4, 63, 64, 127, 128, 10**6)] == [1, 1, 2, 2, 4, 32, 64, 64, 64, 64]
     band = open(os.path.join(CSRC, "fpsq_band.hip")).read()
     assert f"constexpr int kBqMaxGrid = {L.MAX_GRID};" in band
+    # every per-entry launch of the nonlinear model (k_bn_vals, k_bcn_vals, k_bcn_assemble, the gathers of the create and of an
+    # objgrad) takes its grid from ONE helper with that cap: no other launch of the file spells a grid of 256-entry blocks
     nlp = open(os.path.join(CSRC, "fpsq_band_nlp.hip.h")).read()
-    assert nlp.count(f"(b->nnz + 255) / 256, {L.MAX_GRID_FLAT})") == 2   # k_bn_vals and the gathers of the create
+    assert nlp.count(f"dim3 flat_grid(int64_t len) {{ return dim3((unsigned)std::max<int64_t>(std::min<int64_t>((len + 255) / 256, "
+                     f"{L.MAX_GRID_FLAT}), 1)); }}") == 1
+    assert nlp.count("+ 255) / 256") == 1
+    for kernel in ("k_bn_vals", "k_bcn_vals", "k_bcn_assemble", "k_gather_d"):
+        launches = re.findall(rf"hipLaunchKernelGGL\({kernel}, (\w+)", nlp)
+        assert launches and set(launches) <= {"flat_grid", "gz", "gt"}, kernel
+    assert "const dim3 gz = flat_grid(b->nnz), gt = flat_grid(b->t_nnz);" in nlp
 
 
 @pytest.mark.parametrize("name", L.NAMES)
@@ -134,10 +142,27 @@ def test_the_site_table_names_every_dispatch_of_the_band_unit():
     for f in ("fpsq_band.hip", "fpsq_band_nlp.hip.h"):
         src = open(os.path.join(CSRC, f)).read()
         sites += re.findall(r"WITH_LANE_GROUP\((?:qp->|lin\.)?(\w+),.*?\(?(k_\w+)<", src, flags=re.S)
-    assert len(sites) == 26
+    assert len(sites) == 30   # (18 in fpsq_band.hip, 12 in fpsq_band_nlp.hip.h, the model with coupling terms included)
     assert {lg for lg, _ in sites} == {"lgA", "lgT", "lgR", "lg"}
     for _, kernel in sites:
         assert re.search(rf"^\s+{kernel}\b", L.__doc__, flags=re.M), kernel
+
+
+def test_the_widths_the_coupled_cases_reach():
+    """what the site table says the model with coupling terms (the CP forms and the k_bcn_* row kernels) runs at: recomputed
+    from tests/coupled_cases.py, every case of the GPU suite and its `stride`"""
+    import coupled_cases as cc
+
+    reach = {}
+    for name in list(cc.CASES) + ["stride"]:
+        d = cc.data(name)
+        reach[name] = (L.lane_group(d.qp.nnz, d.qp.m), L.lane_group(d.qp.nnz, d.qp.n), L.lane_group(cc.s_pattern(d)[1], d.qp.n))
+    print("\n" + "  ".join(f"{k}: {v}" for k, v in reach.items()))
+    lga, lgt, lgr = ({v[i] for v in reach.values()} for i in range(3))
+    assert (lga, lgt, lgr) == ({2, 4, 16, 32}, {1, 2, 32}, {1, 8})
+    assert reach["stride"] == (2, 1, 1)
+    doc = L.__doc__
+    assert "lgA 2, 4, 16, 32; lgT 1, 2, 32; lgR 1, 8" in doc and "STRIDE at 2 / 1 / 1" in doc
 
 
 @pytest.mark.parametrize("name", L.NAMES)

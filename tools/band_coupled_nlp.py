@@ -4,7 +4,7 @@ h (fpsq_band_nlp_create), everything in HBM:
 
   objgrad     one fpsq_band_nlp_objgrad (values, factorisation, sweeps, products; coupled: + assembly of Wo, + finish)
   hprod 2     fpsq_band_nlp_hprod Val(2)  (coupled: bq_launches' sparse form on Q = diag(qe) - Wo(ys), + k_bcn_hcv)
-  hprod 1     fpsq_band_nlp_hprod Val(1)  (coupled: + k_bcn_finish_h1; ghjvprod walks the partner lists)
+  hprod 1     fpsq_band_nlp_hprod Val(1)  (coupled: + k_bcn_finish_h1; ghjvprod, k_bn_hgv<LG, true>, walks the partner lists)
 
    python tools/band_coupled_nlp.py --shape bilinear --only coupled   # one side, in this process (also the run for a kernel trace)
    python tools/band_coupled_nlp.py --shape bilinear --pairs 5        # both sides in fresh child processes, interleaved
