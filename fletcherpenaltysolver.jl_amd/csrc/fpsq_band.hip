@@ -94,6 +94,8 @@ struct fpsq_band_qp_s {
   int32_t *r_rowptr = nullptr, *r_colind = nullptr;
   double *r_vals = nullptr, *tv = nullptr, *partF = nullptr;
   int lgR = 1, gridR = 1;  // lanes per row of R (lane_group)
+  // rows of R listed apart from the CSR above (fpsq_band.hip.h "LONG ROWS"; fpsq_band_nlp_create_coupled_arrow alone sets it)
+  const fpsq::bq_long_rows* long_rows = nullptr;
   std::vector<void*> allocs;  // every device buffer above: freed by fpsq_band_qp_destroy
 };
 
@@ -1549,6 +1551,9 @@ void bq_launches(fpsq_band b, fpsq_band_qp qp, bool hp, const double* x, const d
     WITH_LANE_GROUP(qp->lgR, WITH_BOOL(hp, HP, hipLaunchKernelGGL((k_bq_pack_sq<LG, HP>), dim3(qp->gridR), dim3(256), 0, s,
                                                                   qp->r_rowptr, qp->r_colind, qp->r_vals, x, qp->q, qp->d,
                                                                   b->xn, qp->partF, n)))
+    if (hp && qp->long_rows)  // (R v)_T of the long rows, before the A product reads xn
+      hipLaunchKernelGGL(k_bq_long_rows<LR_PACK>, dim3(qp->long_rows->cols), dim3(256), 0, s, *qp->long_rows, x,
+                         (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, 0.0, b->xn);
   } else if (!qp->gather_g) {
     WITH_BOOL(hp, HP, hipLaunchKernelGGL(k_bq_pack<HP>, grid256(n), dim3(256), 0, s, x, qp->q, qp->d, b->xn, n))
   }
@@ -1570,6 +1575,9 @@ void bq_launches(fpsq_band b, fpsq_band_qp qp, bool hp, const double* x, const d
     WITH_LANE_GROUP(qp->lgR, hipLaunchKernelGGL(k_bq_jacmul<LG>, dim3(qp->gridR), dim3(256), 0, s, qp->r_rowptr, qp->r_colind,
                                                 qp->r_vals, (const int32_t*)nullptr, (const int32_t*)nullptr, -1.0, qp->tv, 1.0,
                                                 out, n))
+    if (hp && qp->long_rows)
+      hipLaunchKernelGGL(k_bq_long_rows<LR_HV2>, dim3(qp->long_rows->cols), dim3(256), 0, s, *qp->long_rows, x,
+                         (const double*)qp->tv, (const double*)nullptr, (const double*)nullptr, rho, out);
   }
 }
 

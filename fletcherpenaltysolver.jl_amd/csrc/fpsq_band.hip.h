@@ -511,6 +511,76 @@ __global__ __launch_bounds__(256) void k_bq_jacmul(const int32_t* __restrict__ r
   }
 }
 
+// ---- LONG ROWS of R (fpsq_band_nlp_create_coupled_arrow): a long column coupled to the states owns a row of R = -Wo(ys) with up
+// to m entries.  The CSR the lane-group kernels above see holds those rows EMPTY; they are listed behind it in the same index
+// and value arrays (entry k of long row i: [ptr[i], ptr[i + 1]), column col[k], value slot k, contributors
+// [cptr[k], cptr[k + 1]) as fpsq_coupled.h lists them), and each is summed by ONE WORKGROUP in the manner of bn_lc_sums: the
+// threads stride the row, four entries of a thread per trip so that their gathered loads are in flight together, a thread's
+// terms in index order, lanes by xor shuffles, waves in index order; no atomics.  A model view without long rows carries a null
+// pointer and launches nothing of this.
+struct bq_long_rows {
+  int cols = 0;                                                   // long columns = workgroups
+  const int32_t *ptr = nullptr, *col = nullptr, *lcols = nullptr;  // cols + 1, entries, the columns themselves
+  const int32_t *cptr = nullptr, *crow = nullptr;                  // contributor lists (Val(1) sums Wo(q1) from them)
+  const double* cw = nullptr;
+  const double *rv = nullptr, *wq2 = nullptr, *wc = nullptr;       // -Wo(ys), Wo(q2), Wo(c) on the slots
+};
+
+// What row T = lcols[i] lacks behind the launch that walked the other rows of R, by mode:
+//   LR_OBJ   behind k_bcn_finish:     out_T += sum_k (Wo(q2)_Tk gs_k + Wo(ys)_Tk p2_k)                      u0 = gs, u1 = p2
+//   LR_PACK  behind k_bq_pack_sq<HP>: xg[T].y += sum_k R_Tk v_k   (out = xg)                                 u0 = v
+//   LR_HV2   behind k_bq_jacmul on R: out_T -= sum_k R_Tk Ptv_k, and += sum_k Wo(c)_Tk v_k when rho > 0      u0 = v, u1 = Ptv
+//   LR_HV1   behind k_bcn_finish_h1:  out_T += sum_k (rho Wo(c)_Tk v_k - R_Tk Ptv_k - Wo(q1)_Tk gs_k)        u0 = v, u1 = Ptv, u2 = gs,
+//            Wo(q1) from the contributor lists and the first solve's y[p] = {q1, .}
+enum { LR_OBJ = 0, LR_PACK = 1, LR_HV2 = 2, LR_HV1 = 3 };
+
+template <int MODE>
+__device__ __forceinline__ double bq_long_row_term(const bq_long_rows& L, int k, const double* __restrict__ u0,
+                                                   const double* __restrict__ u1, const double* __restrict__ u2,
+                                                   const double* __restrict__ y, double rho) {
+  const int c = L.col[k];
+  if constexpr (MODE == LR_OBJ) {
+    return L.wq2[k] * u0[c] - L.rv[k] * u1[c];
+  } else if constexpr (MODE == LR_PACK) {
+    return L.rv[k] * u0[c];
+  } else if constexpr (MODE == LR_HV2) {
+    const double t = -(L.rv[k] * u1[c]);
+    return rho > 0.0 ? t + L.wc[k] * u0[c] : t;
+  } else {
+    double wq1 = 0.0;
+    const int ue = L.cptr[k + 1];
+    for (int u = L.cptr[k]; u < ue; ++u) wq1 += L.cw[u] * y[(size_t)L.crow[u] * 2];
+    return (rho * L.wc[k]) * u0[c] - L.rv[k] * u1[c] - wq1 * u2[c];
+  }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_bq_long_rows(bq_long_rows L, const double* __restrict__ u0, const double* __restrict__ u1,
+                                                      const double* __restrict__ u2, const double* __restrict__ y, double rho,
+                                                      double* __restrict__ out) {
+  __shared__ double sh[4];
+  const int i = blockIdx.x;
+  double s[1] = {0.0};
+  const int e = L.ptr[i + 1];
+  int k = L.ptr[i] + threadIdx.x;
+  for (; k + 3 * 256 < e; k += 4 * 256) {
+    double t[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t[u] = bq_long_row_term<MODE>(L, k + u * 256, u0, u1, u2, y, rho);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[0] += t[u];
+  }
+  for (; k < e; k += 256) s[0] += bq_long_row_term<MODE>(L, k, u0, u1, u2, y, rho);
+  bq_block_sum(s, sh);
+  if (threadIdx.x == 0) {
+    const int j = L.lcols[i];
+    if constexpr (MODE == LR_PACK)
+      out[(size_t)j * 2 + 1] += s[0];
+    else
+      out[j] += s[0];
+  }
+}
+
 
 // ---- block forms of the product kernels (fpsq_band_qp_hprod_block, fpsq_band_solve_two_least_squares_block): a TILE of up
 // to kBlkVec vectors, vector v of a block at base + v * len (C-contiguous (k, len)), travels through A, the two sweeps

@@ -13,6 +13,10 @@
 // bq_launches' sparse form with Q = diag(qe) - Wo(ys), unchanged.  It is ONE model: the kernels that walk a row of A or of A'
 // take the terms as the compile-time flag CP (one row walk, `if constexpr` where an expression differs), the kernels on the
 // lists and on S (k_bcn_*) have no separable counterpart, and the drivers branch only where a launch differs.
+// fpsq_band_nlp_create_coupled_arrow puts the terms on handles with border rows and long columns: border rows and the entries of
+// long columns are ordinary stored entries to every kernel on the stored CSR and on the lists; the virtual transposed entries
+// of a long column meet no term; and the row of S a long column owns (up to m entries) is listed apart from the CSR the
+// lane-group kernels walk and summed by one workgroup (k_bq_long_rows, fpsq_band.hip.h "LONG ROWS").
 #pragma once
 #include "fpsq_coupled.h"
 
@@ -542,7 +546,9 @@ __global__ __launch_bounds__(256) void k_bn_lc_epilogue(const int32_t* __restric
   }
 }
 
-// hprod Val(1), behind k_bn_epilogue_h1 (whose h1 is 0 at a long column): Hv_j by its formula with the sums above
+// hprod Val(1), behind k_bn_epilogue_h1 (whose h1 is 0 at a long column): Hv_j by its formula with the sums above.  CP: as
+// k_bn_epilogue_h1<LG, true>, vec is the packed pair xg[j] = {v_j, (E v)_j} and (E v)_j stands where qe_j v_j does
+template <bool CP>
 __global__ __launch_bounds__(256) void k_bn_lc_epilogue_h1(const int32_t* __restrict__ lc_ptr, const int32_t* __restrict__ lc_row,
                                                            const int32_t* __restrict__ lc_ent, const int32_t* __restrict__ lcols,
                                                            const double* __restrict__ h, const double* __restrict__ y,
@@ -555,8 +561,14 @@ __global__ __launch_bounds__(256) void k_bn_lc_epilogue_h1(const int32_t* __rest
   bn_lc_sums(lc_ptr, lc_row, lc_ent, h, y, keep, mpad, vgrid, v, sh);
   if (threadIdx.x == 0) {
     const int j = lcols[blockIdx.x];
-    const double vv = vec[j], qv = qe[j];
-    out[j] = (qv * vv - v[1]) - qv * v[0] + 2.0 * sigma * v[0] + rho * (v[2] + hc[j] * vv) + eta * vv - v[3] * gsm[j];
+    if constexpr (CP) {
+      const f64x2 t = *reinterpret_cast<const f64x2*>(vec + (size_t)j * 2);
+      const double vv = t.x, qv = qe[j];
+      out[j] = (t.y - v[1]) - qv * v[0] + 2.0 * sigma * v[0] + rho * (v[2] + hc[j] * vv) + eta * vv - v[3] * gsm[j];
+    } else {
+      const double vv = vec[j], qv = qe[j];
+      out[j] = (qv * vv - v[1]) - qv * v[0] + 2.0 * sigma * v[0] + rho * (v[2] + hc[j] * vv) + eta * vv - v[3] * gsm[j];
+    }
   }
 }
 
@@ -573,7 +585,11 @@ struct bn_terms_s {
   double *pw = nullptr, *tpw = nullptr;
   int32_t *cptr = nullptr, *crow = nullptr;
   double *cw = nullptr, *wq2 = nullptr, *wc = nullptr;
-  int64_t snz = 0;
+  int64_t snz = 0;  // value slots: the entries of S, the long rows' behind those of the CSR
+  // fpsq_band_nlp_create_coupled_arrow on a handle with long columns: their rows of S, listed apart (fpsq_band.hip.h "LONG
+  // ROWS"; lr.cols = 0: none, every row of S is in the CSR)
+  int32_t* lrp = nullptr;
+  bq_long_rows lr;
 };
 
 // fpsq_band_nlp_create: the model's vectors and its two value arrays in the stored row order (a, h: through vperm) and in the
@@ -699,7 +715,7 @@ int band_nlp_make(const char* entry, bool arrow, fpsq_band b, const double* qdia
 }
 
 // The term lists of a model that band_nlp_make has made (fpsq_coupled.h builds them on the host from the handle's structure)
-int band_nlp_attach(fpsq_band b, fpsq_band_nlp nlp, int64_t nterms, const int32_t* t_row, const int32_t* t_j, const int32_t* t_k,
+int band_nlp_attach(const char* entry, fpsq_band b, fpsq_band_nlp nlp, int64_t nterms, const int32_t* t_row, const int32_t* t_j, const int32_t* t_k,
                     const double* t_w) {
   const size_t T = (size_t)nterms, nnz = (size_t)b->nnz, tnz = (size_t)b->t_nnz, n = (size_t)b->n, m = (size_t)b->m;
   std::vector<int32_t> row(T), cj(T), ck(T), rp(m + 1), ci(std::max<size_t>(nnz, 1)), tperm(std::max<size_t>(tnz, 1));
@@ -716,11 +732,20 @@ int band_nlp_attach(fpsq_band b, fpsq_band_nlp nlp, int64_t nterms, const int32_
     rinv.resize(m);
     for (size_t p = 0; p < m; ++p) rinv[b->rperm_host[p]] = (int32_t)p;
   }
+  // the long columns' rows of S apart from the CSR, unless FPSQ_BAND_NLP_LONG_ROWS=0 leaves them to the lane-group kernels
+  std::vector<int32_t> lcols;
+  bool split = b->cols > 0;
+  if (const char* ev = std::getenv("FPSQ_BAND_NLP_LONG_ROWS")) split = split && std::atoi(ev) != 0;
+  if (split) {
+    lcols.resize((size_t)b->cols);
+    CHK(b, hipMemcpy(lcols.data(), b->lc_cols, lcols.size() * 4, hipMemcpyDeviceToHost));
+  }
   CoupledLists L;
   const std::string what = coupled_build((int64_t)n, (int64_t)m, rp.data(), ci.data(), b->reordered ? rinv.data() : nullptr,
-                                         (int64_t)tnz, tperm.data(), nterms, row.data(), cj.data(), ck.data(), w.data(), L);
+                                         (int64_t)tnz, tperm.data(), nterms, row.data(), cj.data(), ck.data(), w.data(), L,
+                                         (int64_t)lcols.size(), lcols.data());
   if (!what.empty()) {
-    b->err = "band_nlp_create_coupled: " + what;
+    b->err = std::string(entry) + ": " + what;
     return FPSQ_ERR_ARG;
   }
   bn_terms_s* cp = &nlp->cp;
@@ -729,15 +754,16 @@ int band_nlp_attach(fpsq_band b, fpsq_band_nlp nlp, int64_t nterms, const int32_
   const size_t snz = L.sci.size(), s4 = std::max<size_t>(snz, 1) * 4, s8 = std::max<size_t>(snz, 1) * 8;
   cp->snz = (int64_t)snz;
   lin.sparse_q = true;
-  lin.lgR = lane_group((int64_t)snz, (int64_t)n);
+  lin.lgR = lane_group((int64_t)L.srp[n], (int64_t)n);  // (from the rows the lane groups walk)
   lin.gridR = bq_grid((int64_t)n, lin.lgR);
   const auto H2D = hipMemcpyHostToDevice;
+  const size_t tp = L.tpcol.size();  // 2 T, less what lies in long columns (their transposed rows are virtual)
   if (!qp_buffers(nlp, {{(void**)&cp->pptr, (nnz + 1) * 4, L.pptr.data(), H2D},
                         {(void**)&cp->pcol, 2 * T * 4, L.pcol.data(), H2D},
                         {(void**)&cp->pw, 2 * T * 8, L.pw.data(), H2D},
                         {(void**)&cp->tpptr, (tnz + 1) * 4, L.tpptr.data(), H2D},
-                        {(void**)&cp->tpcol, 2 * T * 4, L.tpcol.data(), H2D},
-                        {(void**)&cp->tpw, 2 * T * 8, L.tpw.data(), H2D},
+                        {(void**)&cp->tpcol, std::max<size_t>(tp, 1) * 4, tp ? L.tpcol.data() : nullptr, H2D},
+                        {(void**)&cp->tpw, std::max<size_t>(tp, 1) * 8, tp ? L.tpw.data() : nullptr, H2D},
                         {(void**)&cp->tcol, std::max<size_t>(tnz, 1) * 4, tnz ? L.tcol.data() : nullptr, H2D},
                         {(void**)&lin.r_rowptr, (n + 1) * 4, L.srp.data(), H2D},
                         {(void**)&lin.r_colind, s4, L.sci.data(), H2D},
@@ -748,9 +774,23 @@ int band_nlp_attach(fpsq_band b, fpsq_band_nlp nlp, int64_t nterms, const int32_
                         {(void**)&cp->wq2, s8, nullptr, H2D},
                         {(void**)&cp->wc, s8, nullptr, H2D},
                         {(void**)&lin.tv, n * 8, nullptr, H2D},
-                        {(void**)&lin.partF, (size_t)lin.gridR * 8, nullptr, H2D}})) {
-    b->err = "band_nlp_create_coupled: cannot allocate or fill the term lists";
+                        {(void**)&lin.partF, (size_t)lin.gridR * 8, nullptr, H2D},
+                        {(void**)&cp->lrp, L.lrp.size() * 4, L.lrp.data(), H2D}})) {
+    b->err = std::string(entry) + ": cannot allocate or fill the term lists";
     return FPSQ_ERR_HIP;
+  }
+  if (split) {
+    cp->lr.cols = b->cols;
+    cp->lr.ptr = cp->lrp;
+    cp->lr.col = lin.r_colind;
+    cp->lr.lcols = b->lc_cols;
+    cp->lr.cptr = cp->cptr;
+    cp->lr.crow = cp->crow;
+    cp->lr.cw = cp->cw;
+    cp->lr.rv = lin.r_vals;
+    cp->lr.wq2 = cp->wq2;
+    cp->lr.wc = cp->wc;
+    lin.long_rows = &cp->lr;
   }
   return FPSQ_OK;
 }
@@ -775,7 +815,24 @@ int fpsq_band_nlp_create_coupled(fpsq_band b, const double* qdiag, const double*
   fpsq_band_nlp nlp = nullptr;
   if (int rc = band_nlp_make("band_nlp_create_coupled", false, b, qdiag, d, bvec, a_vals, h_vals, &nlp)) return rc;
   if (nterms > 0) {  // (without terms the model IS fpsq_band_nlp_create's: the same launches, the same bits)
-    if (int rc = band_nlp_attach(b, nlp, nterms, t_row, t_j, t_k, t_w)) {
+    if (int rc = band_nlp_attach("band_nlp_create_coupled", b, nlp, nterms, t_row, t_j, t_k, t_w)) {
+      fpsq_band_nlp_destroy(nlp);
+      return rc;
+    }
+  }
+  *out = nlp;
+  return FPSQ_OK;
+}
+
+int fpsq_band_nlp_create_coupled_arrow(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
+                                       const double* h_vals, int64_t nterms, const int32_t* t_row, const int32_t* t_j,
+                                       const int32_t* t_k, const double* t_w, fpsq_band_nlp* out) {
+  if (nterms < 0 || (nterms > 0 && (!t_row || !t_j || !t_k || !t_w))) return FPSQ_ERR_ARG;
+  fpsq_band_nlp nlp = nullptr;
+  if (int rc = band_nlp_make("band_nlp_create_coupled_arrow", true, b, qdiag, d, bvec, a_vals, h_vals, &nlp)) return rc;
+  if (nterms > 0) {  // (without terms the model IS fpsq_band_nlp_create_arrow's; without border rows and long columns the
+                     // lists and launches are fpsq_band_nlp_create_coupled's)
+    if (int rc = band_nlp_attach("band_nlp_create_coupled_arrow", b, nlp, nterms, t_row, t_j, t_k, t_w)) {
       fpsq_band_nlp_destroy(nlp);
       return rc;
     }
@@ -826,6 +883,8 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
                        ax.tile(), b->vals, b->nnz);
     hipLaunchKernelGGL(k_bcn_vals, flat_grid(b->t_nnz), dim3(256), 0, s, nlp->ta, nlp->th, cp.tcol, cp.tpptr, cp.tpcol, cp.tpw,
                        ax.tile(), b->t_vals, b->t_nnz);
+    if (b->fb_nnz > 0)  // (as below)
+      hipLaunchKernelGGL(k_gather_d, flat_grid(b->fb_nnz), dim3(256), 0, s, b->vals, b->fb_perm, b->fb_vals, b->fb_nnz);
   } else if (b->nnz > 0) {
     hipLaunchKernelGGL(k_bn_vals, flat_grid(b->nnz), dim3(256), 0, s, nlp->a, nlp->h, b->colind, ax.tile(), b->vals, b->nnz);
     WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_tvals<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, nlp->ta, nlp->th,
@@ -860,6 +919,9 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
     if (gx)
       WITH_LANE_GROUP(lin.lgR, hipLaunchKernelGGL(k_bcn_finish<LG>, dim3(lin.gridR), dim3(256), 0, s, lin.r_rowptr, lin.r_colind,
                                                   lin.r_vals, cp.wq2, lin.tv, nlp->gs, ogx.tile(), n))
+    if (gx && cp.lr.cols)  // the long columns' rows of S (k_bn_lc_epilogue has rewritten gx there)
+      hipLaunchKernelGGL(k_bq_long_rows<LR_OBJ>, dim3(cp.lr.cols), dim3(256), 0, s, cp.lr, (const double*)nlp->gs,
+                         (const double*)lin.tv, (const double*)nullptr, (const double*)nullptr, 0.0, ogx.tile());
   }
   hipLaunchKernelGGL(k_bq_phi, dim3(1), dim3(256), 0, s, nlp->partP, lin.gridP, nlp->partE, lin.gridE, rho, eta, b->scal);
   for (const StagedArg* o : {&ogx, &ogs, &oys})
@@ -908,10 +970,13 @@ int fpsq_band_nlp_hprod(fpsq_band b, fpsq_band_nlp nlp, const double* v, double 
       hipLaunchKernelGGL(k_bn_hcv, grid256(n), dim3(256), 0, s, nlp->hc, av.tile(), ah.tile(), n);
   } else {
     double* keep = b->cols ? b->bd_keep : b->o_q2;
-    if (coupled)  // xn[j] = {v_j, (E v)_j}, E = diag(qe) - Wo(ys)
+    if (coupled) {  // xn[j] = {v_j, (E v)_j}, E = diag(qe) - Wo(ys)
       WITH_LANE_GROUP(lin.lgR, hipLaunchKernelGGL((k_bq_pack_sq<LG, true>), dim3(lin.gridR), dim3(256), 0, s, lin.r_rowptr,
                                                   lin.r_colind, lin.r_vals, av.tile(), nlp->qe, nlp->d, b->xn, lin.partF, n))
-    else
+      if (cp.lr.cols)
+        hipLaunchKernelGGL(k_bq_long_rows<LR_PACK>, dim3(cp.lr.cols), dim3(256), 0, s, cp.lr, av.tile(), (const double*)nullptr,
+                           (const double*)nullptr, (const double*)nullptr, 0.0, b->xn);
+    } else
       hipLaunchKernelGGL(k_bq_pack<true>, grid256(n), dim3(256), 0, s, av.tile(), nlp->qe, nlp->d, b->xn, n);
     WITH_LANE_GROUP(lin.lgA, hipLaunchKernelGGL((k_bq_prologue<LG, true, false>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr,
                                                 b->colind, b->vals, b->xn, av.tile(), nlp->qe, nlp->d, nlp->bp, b->r2, keep,
@@ -921,13 +986,19 @@ int fpsq_band_nlp_hprod(fpsq_band b, fpsq_band_nlp nlp, const double* v, double 
     WITH_LANE_GROUP(lin.lgT, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
         (k_bn_epilogue_h1<LG, CP>), dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, nlp->th, b->r2, keep,
         CP ? b->xn : av.tile(), nlp->qe, nlp->hc, nlp->gs, sigma, rho, eta, ah.tile(), lin.tv, n)))
-    if (b->cols)  // (H'q1)_j at the long columns, before the second solve takes b->r2
-      hipLaunchKernelGGL(k_bn_lc_epilogue_h1, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->lc_cols, nlp->h,
-                         b->r2, keep, av.tile(), nlp->qe, nlp->hc, nlp->gs, sigma, rho, eta, ah.tile(), mpad, b->bc_grid);
-    if (coupled)  // the rows of S, while b->r2 still holds the first solve
+    if (b->cols) {  // (H'q1)_j at the long columns, before the second solve takes b->r2
+      WITH_BOOL(coupled, CP, hipLaunchKernelGGL(k_bn_lc_epilogue_h1<CP>, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row,
+                                                b->lc_ent, b->lc_cols, nlp->h, b->r2, keep, CP ? b->xn : av.tile(), nlp->qe,
+                                                nlp->hc, nlp->gs, sigma, rho, eta, ah.tile(), mpad, b->bc_grid))
+    }
+    if (coupled) {  // the rows of S, while b->r2 still holds the first solve
       WITH_LANE_GROUP(lin.lgR, hipLaunchKernelGGL(k_bcn_finish_h1<LG>, dim3(lin.gridR), dim3(256), 0, s, lin.r_rowptr,
                                                   lin.r_colind, cp.cptr, cp.crow, cp.cw, lin.r_vals, cp.wc, b->r2, lin.tv,
                                                   av.tile(), nlp->gs, rho, ah.tile(), n))
+      if (cp.lr.cols)
+        hipLaunchKernelGGL(k_bq_long_rows<LR_HV1>, dim3(cp.lr.cols), dim3(256), 0, s, cp.lr, av.tile(), (const double*)lin.tv,
+                           (const double*)nlp->gs, (const double*)b->r2, rho, ah.tile());
+    }
     // z = M^-1 ghjvprod(x, gs, v) = M^-1 H (gs .* v) [+ the terms] on the cached factor (tau = delta, include/fpsq.h), Hv -= J'z
     const bn_partners pt{cp.pptr, cp.pcol, cp.pw};
     WITH_LANE_GROUP(lin.lgA, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(

@@ -7,6 +7,12 @@
 //   S               the n x n pattern of Wo(y) = sum_t w_t y_row(t) (e_j e_k' + e_k e_j'): symmetric, both triangles, no diagonal,
 //                   every row sorted by column.
 //   contributors    per entry of S: the pairs (stored row, w), in increasing stored row, with Wo(y)_jk = sum w y_row.
+// LONG COLUMNS (fpsq_band_nlp_create_coupled_arrow).  The transposed structure of a handle with long columns has virtual entries
+// (t_perm = nnz, the slot behind the stored values): they get an empty partner list and column 0.  A long column coupled to the
+// states owns a row of S with up to m entries; given the list of long columns the builder leaves those rows EMPTY in the CSR
+// (S_band: what the row kernels walk; a long column stays a column of the other rows) and lists them behind it instead: the
+// entries of long row i are [lrp[i], lrp[i + 1]) of the SAME sci / cptr arrays, lrp[0] = srp[n], so an entry's index is its
+// value slot whichever part it lies in.
 #pragma once
 #include <stdint.h>
 
@@ -25,15 +31,26 @@ struct CoupledLists {
   std::vector<int32_t> srp, sci;      // n + 1, nnz(S)
   std::vector<int32_t> cptr, crow;    // nnz(S) + 1, 2 T: contributor lists
   std::vector<double> cw;             // 2 T
+  std::vector<int32_t> lrp;           // long columns + 1: their rows of S behind S_band's entries (lrp[0] = srp[n])
 };
 
 // rp / ci: the STORED CSR of the handle (m rows); rinv: the caller's row -> the stored one (null = identity); t_perm: transposed
 // entry -> stored entry (t_nnz of them).  The terms are in the caller's row order, 0-based.  Returns "" and fills `out`, or what
-// is wrong (without the entry's prefix).
+// is wrong (without the entry's prefix).  lcols: the nlong long columns whose rows of S are listed apart, strictly ascending.
 inline std::string coupled_build(int64_t n, int64_t m, const int32_t* rp, const int32_t* ci, const int32_t* rinv, int64_t t_nnz,
                                  const int32_t* t_perm, int64_t nterms, const int32_t* t_row, const int32_t* t_j,
-                                 const int32_t* t_k, const double* t_w, CoupledLists& out) {
+                                 const int32_t* t_k, const double* t_w, CoupledLists& out, int64_t nlong = 0,
+                                 const int32_t* lcols = nullptr) {
   const int64_t nnz = rp[m];
+  std::vector<int32_t> lidx;  // column -> its place among the long columns, -1: none (empty without long columns)
+  if (nlong > 0) {
+    lidx.assign((size_t)n, -1);
+    for (int64_t i = 0; i < nlong; ++i) {
+      if (lcols[i] < 0 || lcols[i] >= n || (i > 0 && lcols[i] <= lcols[i - 1])) return "the long columns are not ascending columns";
+      lidx[lcols[i]] = (int32_t)i;
+    }
+  }
+  auto is_long = [&](int32_t col) { return !lidx.empty() && lidx[col] >= 0; };
   if (nterms < 0 || 2 * nterms > INT32_MAX) return "the number of terms is out of range";
   const size_t T = (size_t)nterms;
   struct Att { int32_t p, ej, ek; };  // the stored row and the two stored entries of a term
@@ -105,6 +122,10 @@ inline std::string coupled_build(int64_t n, int64_t m, const int32_t* rp, const 
   out.tpw.reserve(2 * T);
   for (int64_t k = 0; k < t_nnz; ++k) {
     const int32_t e = t_perm[k];
+    if (e >= nnz) {  // a virtual entry of a long column: it gathers a = 1, h = 0 and meets no term
+      out.tpptr[k + 1] = (int32_t)out.tpcol.size();
+      continue;
+    }
     out.tcol[k] = ci[e];
     for (int32_t u = out.pptr[e]; u < out.pptr[e + 1]; ++u) {
       out.tpcol.push_back(out.pcol[u]);
@@ -112,7 +133,8 @@ inline std::string coupled_build(int64_t n, int64_t m, const int32_t* rp, const 
     }
     out.tpptr[k + 1] = (int32_t)out.tpcol.size();
   }
-  // S and its contributor lists: both orientations of every term, sorted by (row of S, column of S, stored row)
+  // S and its contributor lists: both orientations of every term, sorted by (row of S, column of S, stored row), the rows of
+  // the long columns behind all others
   struct Tri { int32_t j, k, p; double w; };
   std::vector<Tri> tri;
   tri.reserve(2 * T);
@@ -120,10 +142,12 @@ inline std::string coupled_build(int64_t n, int64_t m, const int32_t* rp, const 
     tri.push_back({t_j[t], t_k[t], att[t].p, t_w[t]});
     tri.push_back({t_k[t], t_j[t], att[t].p, t_w[t]});
   }
-  std::sort(tri.begin(), tri.end(), [](const Tri& a, const Tri& c) {
+  std::sort(tri.begin(), tri.end(), [&](const Tri& a, const Tri& c) {
+    if (is_long(a.j) != is_long(c.j)) return is_long(c.j);
     return a.j != c.j ? a.j < c.j : a.k != c.k ? a.k < c.k : a.p < c.p;
   });
   out.srp.assign((size_t)n + 1, 0);
+  out.lrp.assign((size_t)nlong + 1, 0);
   out.sci.clear();
   out.cptr.assign(1, 0);
   out.crow.assign(2 * T, 0);
@@ -132,13 +156,18 @@ inline std::string coupled_build(int64_t n, int64_t m, const int32_t* rp, const 
     if (i == 0 || tri[i].j != tri[i - 1].j || tri[i].k != tri[i - 1].k) {
       if (i) out.cptr.push_back((int32_t)i);
       out.sci.push_back(tri[i].k);
-      out.srp[tri[i].j + 1]++;
+      if (is_long(tri[i].j))
+        out.lrp[lidx[tri[i].j] + 1]++;
+      else
+        out.srp[tri[i].j + 1]++;
     }
     out.crow[i] = tri[i].p;
     out.cw[i] = tri[i].w;
   }
   if (!tri.empty()) out.cptr.push_back((int32_t)tri.size());
   for (int64_t j = 0; j < n; ++j) out.srp[j + 1] += out.srp[j];
+  out.lrp[0] = out.srp[n];
+  for (int64_t i = 0; i < nlong; ++i) out.lrp[i + 1] += out.lrp[i];
   return "";
 }
 

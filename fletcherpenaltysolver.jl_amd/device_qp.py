@@ -572,6 +572,24 @@ class DeviceBandCoupledQuadNLP(DeviceBandSepQuadNLP):
                 np.ascontiguousarray(nlp_data.t_w, dtype=np.float64))
 
 
+class DeviceArrowBandCoupledQuadNLP(DeviceBandCoupledQuadNLP):
+    """DeviceBandCoupledQuadNLP on an ARROW band (DeviceArrowBandSepQuadNLP's handle): at most `border` long constraint rows and
+    at most `cols` long columns (both 0 .. 16) stay out of the band, and the coupling terms may lie in every row and between
+    every two columns of a row, long columns included -- a free final time or a global parameter MULTIPLIES the dynamics
+    (theta y_k, theta u_k in every row: terms whose second column is a long column; `problems.free_final_time_like`), which
+    neither parent class can state.  The handle comes from `fpsq_band_create_arrow`, the model from
+    `fpsq_band_nlp_create_coupled_arrow` (include/fpsq.h); every method is the base class's and `fps_solve_device` takes the
+    object.  Without terms the model is DeviceArrowBandSepQuadNLP's, on a handle without border rows and long columns
+    DeviceBandCoupledQuadNLP's, bit for bit.  The other keywords are DeviceBandSepQuadNLP's."""
+
+    _create_entry = "fpsq_band_create_arrow"
+    _model_entry = "fpsq_band_nlp_create_coupled_arrow"
+
+    def __init__(self, nlp_data, border=16, cols=16, **kwargs):
+        self._limits = (int(border), int(cols))
+        super().__init__(nlp_data, **kwargs)
+
+
 def rccl_unique_id() -> bytes:
     """128-byte RCCL id (call on rank 0, broadcast, pass to every rank's DeviceEqQP(comm=("rccl", ...)))."""
     lib = _lib.load()

@@ -724,6 +724,6 @@ def fps_solve_device(dev, x0, *, atol=_SE, rtol=_SE, max_iter=100, max_time=300.
     meta = AlgoData(**{k: v for k, v in kwargs.items() if k in AlgoData.__dataclass_fields__})
     dev.sigma, dev.rho, dev.eta = meta.sigma_0, meta.rho_0, 0.0
     dev.set_delta(0.0)
-    # a model with nonlinear constraints (DeviceBandSepQuadNLP, DeviceArrowBandSepQuadNLP: fpsq_band_nlp_*) says so itself
+    # a model with nonlinear constraints (DeviceBandSepQuadNLP, DeviceArrowBandSepQuadNLP, the coupled classes: fpsq_band_nlp_*) says so itself
     penalty = _DeviceNLPPenalty if getattr(dev, "nonlinear", False) else _DevicePenalty
     return _outer_loop(penalty(dev, torch, meta.hessian_approx), x0, meta, atol, rtol, max_iter, max_time, verbose)

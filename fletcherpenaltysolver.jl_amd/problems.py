@@ -311,6 +311,39 @@ def bilinear_control_like(N=2000, tau=0.25, alpha=0.1, seed=1234) -> CoupledQuad
     return _coupled(qp, np.zeros_like(vals), k, 2 * k, 2 * k + 1, np.full(N, -float(tau)))
 
 
+def free_final_time_like(N=2000, tau=0.25, a=1.0, beta=1.0, alpha=0.1, gamma=1.0, theta_hat=1.0, seed=1234) -> CoupledQuadNLP:
+    """Control of y' = -theta (a y - beta u) + s over a horizon whose length theta is a VARIABLE (a free final time scaled to
+    N explicit Euler steps of length tau theta): states y_0 .. y_N and controls u_0 .. u_{N-1} interleaved, then theta,
+    x = (y_0, u_0, y_1, u_1, ..., y_N, theta) (n = 2 N + 2), rows k = 0 .. N - 1
+        y_{k+1} - y_k + tau theta (a y_k - beta u_k) = b_k,
+    and one LONG ROW N, the mean control energy sum_k u_k^2 / (2 N) = b_N (m = N + 1).  theta multiplies the dynamics: row k has
+    the two coupling terms (k, y_k, theta, tau a) and (k, u_k, theta, -tau beta), whose second column is a LONG COLUMN, and four
+    entries -- (k, y_k) = -1, (k, y_{k+1}) = 1 and the EXPLICIT ZEROS (k, u_k), (k, theta) under the terms.  Row N has the N
+    entries (N, u_k) = 0 with the separable curvature h = 1 / N, so a border row carries curvature.  Objective
+    1/2 sum (y - yhat)^2 + alpha/2 sum u^2 + gamma/2 (theta - theta_hat)^2 (up to its constant).  yhat, the states and controls
+    of xhat and x as in bilinear_control_like; theta of xhat is theta_hat (1 + 0.1 (2u - 1)); b makes xhat feasible."""
+    n, m = 2 * N + 2, N + 1
+    th = n - 1
+    k = np.arange(N, dtype=np.int64)
+    rowptr = np.concatenate([4 * np.arange(N + 1, dtype=np.int64), [5 * N]])
+    colind = np.concatenate([np.stack([2 * k, 2 * k + 1, 2 * k + 2, np.full(N, th)], axis=1).ravel(), 2 * k + 1])
+    vals = np.concatenate([np.tile(np.array([-1.0, 0.0, 1.0, 0.0]), N), np.zeros(N)])
+    hvals = np.concatenate([np.zeros(4 * N), np.full(N, 1.0 / N)])
+    idx = np.arange(n, dtype=np.int64)
+    state = (idx % 2 == 0) & (idx < th)
+    ctrl = (idx % 2 == 1) & (idx < th)
+    qdiag = np.where(state, 1.0, np.where(ctrl, alpha, gamma))
+    yhat = 1.0 + 0.5 * np.sin(2.0 * np.pi * (idx // 2) / N)
+    d = np.where(state, -yhat, np.where(ctrl, 0.0, -gamma * theta_hat))
+    u3, u4 = 2.0 * uniform01(seed, idx, 3) - 1.0, 2.0 * uniform01(seed, idx, 4) - 1.0
+    xhat = np.where(state, 1.0 + 0.3 * u3, np.where(ctrl, 0.5 * u3, theta_hat * (1.0 + 0.1 * u3)))
+    x = xhat + 0.1 * u4
+    qp = EqQP(f"free-final-time-N{N}", n, m, rowptr.astype(np.int32), colind.astype(np.int32), vals, qdiag, d, np.zeros(m), x,
+              xhat)   # (qp.b is the LINEAR constraints' and is not used)
+    return _coupled(qp, hvals, np.concatenate([k, k]), np.concatenate([2 * k, 2 * k + 1]), np.full(2 * N, th),
+                    np.concatenate([np.full(N, tau * a), np.full(N, -tau * beta)]))
+
+
 def _stratified_rows(m, n, per_row, start, width, seed, diag_col=None, diag_boost=0.0):
     """Each of the m rows gets `per_row` sorted, distinct columns: one per stratum of
     [start[i], start[i] + width).  If diag_col is given, the stratum containing diag_col[i] is

@@ -638,6 +638,22 @@ int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
  *                         the same bits.  With terms an objgrad is 8 launches besides the factorisation and the sweeps (the
  *                         separable model: 6), hprod Val(2) 4 or 5 (3 or 4), Val(1) 6 (5); S = the pattern of Wo, its contributor
  *                         lists and the per-entry partner lists are built at create.
+ *   fpsq_band_nlp_create_coupled_arrow  fpsq_band_nlp_create_coupled's parameter list, checks, messages and formulas for a
+ *                         handle of ANY kind but a fpsq_band_create_coo* one (FPSQ_ERR_STATE, fpsq_band_nlp_create's message), as
+ *                         fpsq_band_nlp_create_arrow takes them: a free final time or a global parameter that multiplies the
+ *                         dynamics is a coupling term whose second column is a long column.  Terms may lie in band rows and in
+ *                         border rows, between two band columns, a band column and a long column, or two long columns.  The
+ *                         state rules and soft codes are unchanged; a failing border pivot is reported or regularised as on
+ *                         fpsq_band_nlp_create_arrow.  With nterms = 0 the model IS fpsq_band_nlp_create_arrow's on that handle,
+ *                         on a handle without border rows and long columns it IS fpsq_band_nlp_create_coupled's: the same
+ *                         launches, the same bits.  A long column coupled to the states owns a row of S with up to m entries:
+ *                         those rows are kept out of the CSR the lane-group kernels walk (there they are empty) and summed by
+ *                         one workgroup per long column, in a fixed order and without atomics.  Launches besides the
+ *                         factorisation and the sweeps, on a handle with long columns: an objgrad 11 (fpsq_band_nlp_create_arrow:
+ *                         8; one more each when the band is formed by row pairs), hprod Val(2) 7 or 8 (the separable model on
+ *                         that handle: 4 or 5), Val(1) 10 (7).  FPSQ_BAND_NLP_LONG_ROWS=0, read at create, leaves the long rows
+ *                         inside S for the lane-group kernels (one launch fewer per objgrad, two per hprod): the independent form
+ *                         the split one is measured and cross-checked against (profiles/band_coupled_arrow_nlp.md).
  * Destroy a model before the handle it was created on. */
 typedef struct fpsq_band_nlp_s *fpsq_band_nlp;
 int fpsq_band_nlp_create(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
@@ -648,6 +664,10 @@ int fpsq_band_nlp_create_coupled(fpsq_band b, const double *qdiag, const double 
                                  const double *a_vals, const double *h_vals,
                                  int64_t nterms, const int32_t *t_row, const int32_t *t_j, const int32_t *t_k,
                                  const double *t_w, fpsq_band_nlp *out);
+int fpsq_band_nlp_create_coupled_arrow(fpsq_band b, const double *qdiag, const double *d, const double *bvec,
+                                       const double *a_vals, const double *h_vals,
+                                       int64_t nterms, const int32_t *t_row, const int32_t *t_j, const int32_t *t_k,
+                                       const double *t_w, fpsq_band_nlp *out);
 int fpsq_band_nlp_destroy(fpsq_band_nlp nlp);
 int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double *x, double sigma, double rho, double eta, double delta,
                           const double *xk, double *fx, double *gx, double *ys, double *gs, int32_t *info);

@@ -14,6 +14,9 @@ and the bits of fx.  A line belongs to one evaluation, so a differing line names
   coupled-lg  DeviceBandCoupledQuadNLP    with_coupled_constraints(pairs=2, seed=7) on every case of tests/lane_group_cases.py: the
                                           kernels with the flag CP at all seven widths (one-entry rows get no terms, so every
                                           shape is admissible)
+  coupled-arrow  DeviceArrowBandCoupledQuadNLP  every case of tests/coupled_arrow_cases.py.  NOT among the defaults: a build from
+                                          before fpsq_band_nlp_create_coupled_arrow lacks the entry (name it in --models to compare
+                                          two builds that have it)
 Accuracy is the tests' business."""
 import argparse
 import hashlib
@@ -61,7 +64,8 @@ if args.other_lib:   # this process never opens the GPU: each build evaluates in
 
 import fps_amd  # noqa: E402,F401
 from fps_amd import _lib, problems  # noqa: E402
-from fps_amd.device_qp import DeviceArrowBandSepQuadNLP, DeviceBandCoupledQuadNLP, DeviceBandSepQuadNLP  # noqa: E402
+from fps_amd.device_qp import (DeviceArrowBandCoupledQuadNLP, DeviceArrowBandSepQuadNLP, DeviceBandCoupledQuadNLP,  # noqa: E402
+                               DeviceBandSepQuadNLP)
 import coupled_cases as cc  # noqa: E402
 import lane_group_cases as L  # noqa: E402
 
@@ -110,5 +114,11 @@ for model in args.models.split(","):
         for name in L.NAMES:
             data = problems.with_coupled_constraints(L.qp(name), curv=L.CURV, pairs=2, seed=7)
             evaluate(model, name, DeviceBandCoupledQuadNLP(data, **kw))
+    elif model == "coupled-arrow":
+        import coupled_arrow_cases as ca
+
+        for name in ca.NAMES:
+            border, cols = ca.limits(name)
+            evaluate(model, name, DeviceArrowBandCoupledQuadNLP(ca.problem(name)[0], border=border, cols=cols, **kw))
     else:
         raise SystemExit(f"unknown model {model}")
