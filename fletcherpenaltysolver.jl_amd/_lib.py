@@ -146,6 +146,7 @@ SYMBOLS = [
     ("fpsq_band_set_input_stream", C.c_int, [_VP, _I32, _VP]),
     ("fpsq_band_nlp_create", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.POINTER(_VP)]),
     ("fpsq_band_nlp_create_arrow", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.POINTER(_VP)]),
+    ("fpsq_band_nlp_create_fn", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, _VP, C.POINTER(_VP)]),
     ("fpsq_band_nlp_create_coupled", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.c_int64, _VP, _VP, _VP, _DP, C.POINTER(_VP)]),
     ("fpsq_band_nlp_create_coupled_arrow", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.c_int64, _VP, _VP, _VP, _DP, C.POINTER(_VP)]),
     ("fpsq_band_nlp_destroy", C.c_int, [_VP]),

@@ -18,6 +18,8 @@
 // of a long column meet no term; and the row of S a long column owns (up to m entries) is listed apart from the CSR the
 // lane-group kernels walk and summed by one workgroup (k_bq_long_rows, fpsq_band.hip.h "LONG ROWS").
 #pragma once
+#include <limits>
+
 #include "fpsq_coupled.h"
 
 namespace fpsq {
@@ -55,6 +57,129 @@ __global__ __launch_bounds__(256) void k_bn_tvals(const int32_t* __restrict__ t_
   }
 }
 
+// ---- FUNCTION TERMS (fpsq_band_nlp_create_fn): c_i(x) = sum_j (A_ij x_j + H_ij phi_kij(x_j)) - b_i with phi from the table
+// FPSQ_FN_* (include/fpsq.h), one code byte per entry.  J(x)_ij = A_ij + H_ij phi'(x_j) keeps the pattern and the curvature
+// coefficient becomes an array every objgrad rewrites, G(x)_ij = H_ij phi''(x_j): the kernels that read h / th next to J
+// (k_bn_epilogue, k_bn_epilogue_h1, k_bn_hgv, the long-column sums) are handed g / tg and stay as they are.  New are the two
+// value kernels below and the forms of the prologue (FN) and of k_bn_cons that no longer know c from J by the quadratic identity.
+
+// phi, phi', phi'' of function `code` at x.  ONE device function and one expression for every kernel that needs a value, with
+// contraction off, so that the stored and the transposed value arrays get the same bits whatever surrounds the call
+__device__ __forceinline__ void bn_fn_eval(int code, double x, double& p0, double& p1, double& p2) {
+#pragma clang fp contract(off)
+  switch (code) {
+    case FPSQ_FN_HALFSQ:
+      p1 = x;
+      p2 = 1.0;
+      p0 = 0.5 * x * x;
+      break;
+    case FPSQ_FN_CUBE6:
+      p2 = x;
+      p1 = 0.5 * x * x;
+      p0 = p1 * x * (1.0 / 3.0);
+      break;
+    case FPSQ_FN_SIN: {
+      const double sv = sin(x);
+      p0 = sv;
+      p1 = cos(x);
+      p2 = -sv;
+    } break;
+    case FPSQ_FN_COS: {
+      const double cv = cos(x);
+      p0 = cv;
+      p1 = -sin(x);
+      p2 = -cv;
+    } break;
+    case FPSQ_FN_EXP:
+      p0 = p1 = p2 = exp(x);
+      break;
+    default: {  // FPSQ_FN_TANH (the create entry refuses every other code)
+      const double tv = tanh(x), uv = 1.0 - tv * tv;
+      p0 = tv;
+      p1 = uv;
+      p2 = -2.0 * tv * uv;
+    } break;
+  }
+}
+
+// the J value and the curvature coefficient of one entry from its function's derivatives (both value kernels)
+__device__ __forceinline__ void bn_fn_jg(double a, double h, double p1, double p2, double& jv, double& gv) {
+#pragma clang fp contract(off)
+  jv = a + h * p1;
+  gv = h * p2;
+}
+
+// The function form of k_bn_vals: vals[k] = a[k] + h[k] phi'(x_c) (J(x)), g[k] = h[k] phi''(x_c) (G(x)) and the remainder
+// rem[k] = h[k] (phi'(x_c) x_c - phi(x_c)), with which the prologue has c_p = sum_k (J_k x_c - rem_k) - b_p.  A non-finite J value
+// (exp overflows above 709) raises *flag: every thread that sees one stores the same 1, the driver reads the word before it
+// factorises and clears it after it has fired
+__global__ __launch_bounds__(256) void k_bn_vals_fn(const double* __restrict__ a, const double* __restrict__ h,
+                                                    const uint8_t* __restrict__ code, const int32_t* __restrict__ colind,
+                                                    const double* __restrict__ x, double* __restrict__ vals,
+                                                    double* __restrict__ g, double* __restrict__ rem, int32_t* __restrict__ flag,
+                                                    int64_t nnz) {
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < nnz; k += (int64_t)gridDim.x * 256) {
+    const double xv = x[colind[k]], hv = h[k];
+    double p0, p1, p2, jv, gv;
+    bn_fn_eval(code[k], xv, p0, p1, p2);
+    bn_fn_jg(a[k], hv, p1, p2, jv, gv);
+    vals[k] = jv;
+    g[k] = gv;
+    rem[k] = hv * (p1 * xv - p0);
+    if (!isfinite(jv)) *flag = 1;
+  }
+}
+
+// The function form of k_bn_tvals, a lane group per row j: t_vals[k] = ta[k] + th[k] phi'(x_j), tg[k] = th[k] phi''(x_j).  x_j is
+// read once per row and phi', phi'' are evaluated once per function code PRESENT in the row (the lanes' code bits joined by xor
+// shuffles), not per entry; an entry picks its pair by its code.  The virtual entries of a long column have code 0, ta = 1,
+// th = 0: J' gathers 1 and G' is 0 there
+template <int LG>
+__global__ __launch_bounds__(256) void k_bn_tvals_fn(const int32_t* __restrict__ t_rowptr, const double* __restrict__ ta,
+                                                     const double* __restrict__ th, const uint8_t* __restrict__ tcode,
+                                                     const double* __restrict__ x, double* __restrict__ t_vals,
+                                                     double* __restrict__ tg, int n) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (n + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int j = tile * RPB + g;
+    int lo = 0, e = 0;
+    double xv = 0.0;
+    if (j < n) {
+      xv = x[j];
+      lo = t_rowptr[j];
+      e = t_rowptr[j + 1];
+    }
+    int present = 0;
+    for (int k = lo + l; k < e; k += LG) present |= 1 << tcode[k];
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) present |= __shfl_xor(present, o);
+    double d1[FPSQ_FN_COUNT], d2[FPSQ_FN_COUNT];
+#pragma unroll
+    for (int c = 0; c < FPSQ_FN_COUNT; ++c) {
+      d1[c] = d2[c] = 0.0;
+      if ((present >> c) & 1) {
+        double p0;
+        bn_fn_eval(c, xv, p0, d1[c], d2[c]);
+      }
+    }
+    for (int k = lo + l; k < e; k += LG) {
+      const int code = tcode[k];
+      double p1 = d1[0], p2 = d2[0];
+#pragma unroll
+      for (int c = 1; c < FPSQ_FN_COUNT; ++c) {
+        p1 = code == c ? d1[c] : p1;
+        p2 = code == c ? d2[c] : p2;
+      }
+      double jv, gv;
+      bn_fn_jg(ta[k], th[k], p1, p2, jv, gv);
+      t_vals[k] = jv;
+      tg[k] = gv;
+    }
+  }
+}
+
 // With coupling terms: vals[k] = a[k] + h[k] x[col[k]] + sum_u pw[u] x[pcol[u]] over the entries of ONE CSR and their partner
 // lists: launched on the stored structure (col = colind) and on the transposed one (col = the entry's own column, its lists in
 // the same order), so both value arrays get the same bits
@@ -74,8 +199,9 @@ __global__ __launch_bounds__(256) void k_bcn_vals(const double* __restrict__ a, 
 // xg[c] = {g_c, x_c} (k_bq_pack<false>): r[p] = {(J g)_p, -c_p} where the sweeps read it (zero on the padding), keep[p] = c_p;
 // part[2 blk] = this workgroup's slice of f = x.(1/2 q x + d), part[2 blk + 1] = of c.c.  Separable: ha = h and
 // c_p = sum (J - 1/2 h x_c) x_c - b_p.  CP: ha = a and c_p = sum 1/2 (J + a) x_c - b_p, which holds for a symmetric curvature of
-// any kind and needs no walk of the term lists (J = vals already holds them).
-template <int LG, bool CP>
+// any kind and needs no walk of the term lists (J = vals already holds them).  FN (function terms): ha = rem and
+// c_p = sum (J x_c - rem) - b_p, the remainder k_bn_vals_fn left next to J.
+template <int LG, bool CP, bool FN = false>
 __global__ __launch_bounds__(256) void k_bn_prologue(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
                                                      const double* __restrict__ vals, const double* __restrict__ ha,
                                                      const double* __restrict__ xg, const double* __restrict__ x,
@@ -97,7 +223,9 @@ __global__ __launch_bounds__(256) void k_bn_prologue(const int32_t* __restrict__
         const double jv = vals[k], hv = ha[k], av = hv;  // (the one array under the name each form knows it by)
         const f64x2 t = *reinterpret_cast<const f64x2*>(xg + (size_t)colind[k] * 2);
         a0 += jv * t.x;
-        if constexpr (CP)
+        if constexpr (FN)
+          a1 += jv * t.y - hv;
+        else if constexpr (CP)
           a1 += (0.5 * (jv + av)) * t.y;
         else
           a1 += (jv - 0.5 * hv * t.y) * t.y;
@@ -161,6 +289,34 @@ __global__ __launch_bounds__(256) void k_bn_cons(const int32_t* __restrict__ row
         } else {
           s += (a[k] + 0.5 * h[k] * xv) * xv;
         }
+      }
+    }
+#pragma unroll
+    for (int o = LG / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (l == 0 && p < m) c[rperm ? rperm[p] : p] = s - bp[p];
+  }
+}
+
+// The function form of k_bn_cons: c_p = sum (a x_c + h phi(x_c)) - b_p from the model's own arrays and code bytes
+template <int LG>
+__global__ __launch_bounds__(256) void k_bn_cons_fn(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind,
+                                                    const double* __restrict__ a, const double* __restrict__ h,
+                                                    const uint8_t* __restrict__ code, const double* __restrict__ x,
+                                                    const double* __restrict__ bp, const int32_t* __restrict__ rperm,
+                                                    double* __restrict__ c, int m) {
+  constexpr int RPB = 256 / LG;
+  const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+  const int ntiles = (m + RPB - 1) / RPB;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int p = tile * RPB + g;
+    double s = 0.0;
+    if (p < m) {
+      const int e = rowptr[p + 1];
+      for (int k = rowptr[p] + l; k < e; k += LG) {
+        const double xv = x[colind[k]];
+        double p0, p1, p2;
+        bn_fn_eval(code[k], xv, p0, p1, p2);
+        s += a[k] * xv + h[k] * p0;
       }
     }
 #pragma unroll
@@ -603,6 +759,15 @@ struct fpsq_band_nlp_s {
   double *q = nullptr, *d = nullptr, *bp = nullptr;  // n, n, m (b in the STORED row order)
   double *a = nullptr, *h = nullptr, *ta = nullptr, *th = nullptr;  // nnz (+ the virtual entries' slot), t_nnz
   double *qe = nullptr, *hc = nullptr, *gs = nullptr;               // q - H'ys, H'c, gs of the last successful objgrad
+  // fpsq_band_nlp_create_fn with a code other than 0: the code bytes in both orders (the virtual entries' slot holds 0), and what
+  // every objgrad rewrites -- g = G(x) and tg, its transposed order, which the kernels get where the other models hand them
+  // h / th (curv() / tcurv()), rem (k_bn_vals_fn) -- and the word a non-finite J(x) raises
+  bool fn = false;
+  uint8_t *code = nullptr, *tcode = nullptr;
+  double *g = nullptr, *tg = nullptr, *rem = nullptr;
+  int32_t* flag = nullptr;
+  const double* curv() const { return fn ? g : h; }
+  const double* tcurv() const { return fn ? tg : th; }
   double *partP = nullptr, *partE = nullptr;
   fpsq_band_qp_s lin;
   uint64_t fact_gen = 0;   // the handle's factorisation count when that objgrad ended
@@ -808,6 +973,55 @@ int fpsq_band_nlp_create_arrow(fpsq_band b, const double* qdiag, const double* d
   return band_nlp_make("band_nlp_create_arrow", true, b, qdiag, d, bvec, a_vals, h_vals, out);
 }
 
+int fpsq_band_nlp_create_fn(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
+                            const double* h_vals, const uint8_t* fn_codes, fpsq_band_nlp* out) {
+  static const char* entry = "band_nlp_create_fn";
+  if (!b || !out) return FPSQ_ERR_ARG;
+  const size_t nnz = (size_t)b->nnz, tnz = (size_t)b->t_nnz;
+  std::vector<uint8_t> codes(nnz + 1, 0);  // (the slot behind the stored entries: what the virtual transposed entries gather)
+  bool any = false;
+  if (fn_codes && nnz > 0 && b->coo_nnz < 0) {
+    hipSetDevice(b->device);
+    CHK(b, hipMemcpy(codes.data(), fn_codes, nnz, hipMemcpyDefault));
+    for (size_t k = 0; k < nnz; ++k) {
+      if (codes[k] >= FPSQ_FN_COUNT) {
+        b->err = std::string(entry) + ": fn_codes[" + std::to_string(k) + "] = " + std::to_string((int)codes[k]) +
+                 " is not a function code (0 .. " + std::to_string(FPSQ_FN_COUNT - 1) + ")";
+        return FPSQ_ERR_ARG;
+      }
+      any = any || codes[k] != 0;
+    }
+  }
+  fpsq_band_nlp nlp = nullptr;
+  if (int rc = band_nlp_make(entry, true, b, qdiag, d, bvec, a_vals, h_vals, &nlp)) return rc;
+  if (any) {  // (with every code 0 the model IS fpsq_band_nlp_create_arrow's: the same launches, the same bits)
+    std::vector<int32_t> perm(std::max(nnz, tnz));
+    std::vector<uint8_t> st(codes), tr(std::max<size_t>(tnz, 1), 0);
+    bool ok = true;
+    if (b->reordered) {
+      ok = hipMemcpy(perm.data(), b->vperm, nnz * 4, hipMemcpyDeviceToHost) == hipSuccess;
+      for (size_t k = 0; ok && k < nnz; ++k) st[k] = codes[perm[k]];
+    }
+    ok = ok && hipMemcpy(perm.data(), b->t_perm, tnz * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    for (size_t k = 0; ok && k < tnz; ++k) tr[k] = st[perm[k]];
+    const auto H2D = hipMemcpyHostToDevice;
+    ok = ok && qp_buffers(nlp, {{(void**)&nlp->code, nnz + 1, st.data(), H2D},
+                                {(void**)&nlp->tcode, tr.size(), tr.data(), H2D},
+                                {(void**)&nlp->g, nnz * 8, nullptr, H2D},
+                                {(void**)&nlp->tg, std::max<size_t>(tnz, 1) * 8, nullptr, H2D},
+                                {(void**)&nlp->rem, nnz * 8, nullptr, H2D},
+                                {(void**)&nlp->flag, 8, nullptr, H2D}});
+    if (!ok || hipMemset(nlp->flag, 0, 8) != hipSuccess) {
+      b->err = std::string(entry) + ": cannot allocate or fill the function codes";
+      fpsq_band_nlp_destroy(nlp);
+      return FPSQ_ERR_HIP;
+    }
+    nlp->fn = true;
+  }
+  *out = nlp;
+  return FPSQ_OK;
+}
+
 int fpsq_band_nlp_create_coupled(fpsq_band b, const double* qdiag, const double* d, const double* bvec, const double* a_vals,
                                  const double* h_vals, int64_t nterms, const int32_t* t_row, const int32_t* t_j,
                                  const int32_t* t_k, const double* t_w, fpsq_band_nlp* out) {
@@ -850,9 +1064,12 @@ int fpsq_band_nlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* 
   const StagedArg oc = staged(b, c, b->o_q1, (size_t)b->m);
   const int lg = nlp->lin.lgA;
   const bn_partners pt{nlp->cp.pptr, nlp->cp.pcol, nlp->cp.pw};
-  WITH_LANE_GROUP(lg, WITH_BOOL(nlp->coupled, CP, hipLaunchKernelGGL(
+  // (one dispatch on the lane group: the separable and the coupled form, or with function terms k_bn_cons_fn in their place)
+  WITH_LANE_GROUP(lg, if (!nlp->fn) { WITH_BOOL(nlp->coupled, CP, hipLaunchKernelGGL(
       (k_bn_cons<LG, CP>), dim3(bq_grid(b->m, lg)), dim3(256), 0, b->stream, b->rowptr, b->colind, nlp->a, nlp->h, ax.tile(),
-      nlp->bp, b->row_perm(), oc.tile(), (int)b->m, pt)))
+      nlp->bp, b->row_perm(), oc.tile(), (int)b->m, pt)) } else hipLaunchKernelGGL(
+      k_bn_cons_fn<LG>, dim3(bq_grid(b->m, lg)), dim3(256), 0, b->stream, b->rowptr, b->colind, nlp->a, nlp->h, nlp->code, ax.tile(),
+      nlp->bp, b->row_perm(), oc.tile(), (int)b->m))
   if (int rc = stage_back(b, oc)) return rc;
   CHK(b, hipStreamSynchronize(b->stream));
   return FPSQ_OK;
@@ -885,12 +1102,30 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
                        ax.tile(), b->t_vals, b->t_nnz);
     if (b->fb_nnz > 0)  // (as below)
       hipLaunchKernelGGL(k_gather_d, flat_grid(b->fb_nnz), dim3(256), 0, s, b->vals, b->fb_perm, b->fb_vals, b->fb_nnz);
-  } else if (b->nnz > 0) {
-    hipLaunchKernelGGL(k_bn_vals, flat_grid(b->nnz), dim3(256), 0, s, nlp->a, nlp->h, b->colind, ax.tile(), b->vals, b->nnz);
-    WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_tvals<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, nlp->ta, nlp->th,
-                                                ax.tile(), b->t_vals, n))
+  } else if (b->nnz > 0) {  // (with function terms: the function forms of the two launches, which also write G(x) and rem)
+    if (!nlp->fn)
+      hipLaunchKernelGGL(k_bn_vals, flat_grid(b->nnz), dim3(256), 0, s, nlp->a, nlp->h, b->colind, ax.tile(), b->vals, b->nnz);
+    else
+      hipLaunchKernelGGL(k_bn_vals_fn, flat_grid(b->nnz), dim3(256), 0, s, nlp->a, nlp->h, nlp->code, b->colind, ax.tile(), b->vals,
+                         nlp->g, nlp->rem, nlp->flag, b->nnz);
+    WITH_LANE_GROUP(lin.lgT, if (!nlp->fn) hipLaunchKernelGGL(k_bn_tvals<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, nlp->ta,
+                                                              nlp->th, ax.tile(), b->t_vals, n);
+                    else hipLaunchKernelGGL(k_bn_tvals_fn<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, nlp->ta, nlp->th,
+                                            nlp->tcode, ax.tile(), b->t_vals, nlp->tg, n))
     if (b->fb_nnz > 0)  // (long columns and k_band_form: the values of the other columns alone, as fpsq_band_factorize)
       hipLaunchKernelGGL(k_gather_d, flat_grid(b->fb_nnz), dim3(256), 0, s, b->vals, b->fb_perm, b->fb_vals, b->fb_nnz);
+    if (nlp->fn) {  // a non-finite J(x) must not reach the factorisation: what a failed one returns, before one is enqueued
+      int32_t* raised = reinterpret_cast<int32_t*>(b->scal_host + 7);  // (pinned; the scalars of a call end at [4])
+      CHK(b, hipMemcpyAsync(raised, nlp->flag, 4, hipMemcpyDeviceToHost, s));
+      CHK(b, hipStreamSynchronize(s));
+      if (*raised) {
+        CHK(b, hipMemsetAsync(nlp->flag, 0, 4, s));
+        b->err = "band_nlp_objgrad: J(x) holds a non-finite value (nothing was factorised or evaluated)";
+        *fx = std::numeric_limits<double>::quiet_NaN();
+        if (info) *info = -1;
+        return 1;
+      }
+    }
   }
   // 2: the numeric factorisation on them
   if (int rc = band_factor_numeric(b, delta, info)) return rc;  // (1: no valid factor, *info says where; nothing is evaluated)
@@ -900,17 +1135,19 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
                   oys = staged(b, ys, b->o_q1, (size_t)m);
   double* keep = b->cols ? b->bd_keep : b->o_q2;  // (long columns: the operand has virtual rows, as in bq_launches)
   hipLaunchKernelGGL(k_bq_pack<false>, grid256(n), dim3(256), 0, s, ax.tile(), nlp->q, nlp->d, b->xn, n);
-  WITH_LANE_GROUP(lin.lgA, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
+  WITH_LANE_GROUP(lin.lgA, if (!nlp->fn) { WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
       (k_bn_prologue<LG, CP>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, CP ? nlp->a : nlp->h, b->xn,
-      ax.tile(), nlp->q, nlp->d, nlp->bp, b->r2, keep, nlp->partP, m, mpad, n)))
+      ax.tile(), nlp->q, nlp->d, nlp->bp, b->r2, keep, nlp->partP, m, mpad, n)) } else hipLaunchKernelGGL(
+      (k_bn_prologue<LG, false, true>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, nlp->rem, b->xn,
+      ax.tile(), nlp->q, nlp->d, nlp->bp, b->r2, keep, nlp->partP, m, mpad, n))
   if (b->cols) cols_keep<1>(b, keep);
   band_solve(b);
   WITH_LANE_GROUP(lin.lgT, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
-      (k_bn_epilogue<LG, CP>), dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, nlp->th, b->r2, keep,
+      (k_bn_epilogue<LG, CP>), dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, nlp->tcurv(), b->r2, keep,
       b->row_perm(), ax.tile(), axk.tile(), nlp->q, nlp->d, sigma, rho, eta, ogx.tile(), ogs.tile(), oys.tile(), nlp->qe, nlp->hc,
       nlp->gs, lin.tv, nlp->partE, n, m)))
   if (b->cols)  // the curvature sums at the long columns, whose transposed rows are virtual
-    hipLaunchKernelGGL(k_bn_lc_epilogue, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->lc_cols, nlp->h,
+    hipLaunchKernelGGL(k_bn_lc_epilogue, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->lc_cols, nlp->curv(),
                        b->r2, keep, ax.tile(), axk.tile(), nlp->q, nlp->gs, sigma, rho, eta, ogx.tile(), nlp->qe, nlp->hc, mpad,
                        b->bc_grid);
   if (coupled) {  // the values of Wo on S, then the rows of S that gx lacks
@@ -984,11 +1221,11 @@ int fpsq_band_nlp_hprod(fpsq_band b, fpsq_band_nlp nlp, const double* v, double 
     if (b->cols) cols_keep<1>(b, keep);
     band_solve(b);
     WITH_LANE_GROUP(lin.lgT, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
-        (k_bn_epilogue_h1<LG, CP>), dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, nlp->th, b->r2, keep,
+        (k_bn_epilogue_h1<LG, CP>), dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, nlp->tcurv(), b->r2, keep,
         CP ? b->xn : av.tile(), nlp->qe, nlp->hc, nlp->gs, sigma, rho, eta, ah.tile(), lin.tv, n)))
     if (b->cols) {  // (H'q1)_j at the long columns, before the second solve takes b->r2
       WITH_BOOL(coupled, CP, hipLaunchKernelGGL(k_bn_lc_epilogue_h1<CP>, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row,
-                                                b->lc_ent, b->lc_cols, nlp->h, b->r2, keep, CP ? b->xn : av.tile(), nlp->qe,
+                                                b->lc_ent, b->lc_cols, nlp->curv(), b->r2, keep, CP ? b->xn : av.tile(), nlp->qe,
                                                 nlp->hc, nlp->gs, sigma, rho, eta, ah.tile(), mpad, b->bc_grid))
     }
     if (coupled) {  // the rows of S, while b->r2 still holds the first solve
@@ -1002,7 +1239,7 @@ int fpsq_band_nlp_hprod(fpsq_band b, fpsq_band_nlp nlp, const double* v, double 
     // z = M^-1 ghjvprod(x, gs, v) = M^-1 H (gs .* v) [+ the terms] on the cached factor (tau = delta, include/fpsq.h), Hv -= J'z
     const bn_partners pt{cp.pptr, cp.pcol, cp.pw};
     WITH_LANE_GROUP(lin.lgA, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
-        (k_bn_hgv<LG, CP>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, nlp->h, nlp->gs, av.tile(), b->r2, m, mpad,
+        (k_bn_hgv<LG, CP>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, nlp->curv(), nlp->gs, av.tile(), b->r2, m, mpad,
         pt)))
     band_solve(b);
     WITH_LANE_GROUP(lin.lgT, hipLaunchKernelGGL(k_bn_jtz<LG>, dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind,

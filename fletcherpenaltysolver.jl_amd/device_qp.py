@@ -590,6 +590,52 @@ class DeviceArrowBandCoupledQuadNLP(DeviceBandCoupledQuadNLP):
         super().__init__(nlp_data, **kwargs)
 
 
+class DeviceBandSepFuncNLP(DeviceBandSepQuadNLP):
+    """DeviceBandSepQuadNLP with an ELEMENTWISE FUNCTION on every curvature entry (`nlp_data`: a `problems.SepFuncNLP` --
+    `problems.with_function_constraints`, `problems.pendulum_like`; host view: `nlpmodels.SepFuncConModel`):
+    c_i(x) = sum_j (A_ij x_j + H_ij phi(x_j)) - b_i with phi from the table FPSQ_FN_* of include/fpsq.h by the entry's code byte
+    (1/2 x^2, x^3/6, sin, cos, exp, tanh).  The model comes from `fpsq_band_nlp_create_fn`; every method is the base class's
+    and `fps_solve_device` takes the object unchanged.  With every code 0 the model is DeviceBandSepQuadNLP's, bit for bit.
+    An objgrad whose J(x) holds a non-finite value (exp above 709) returns (nan, 1) like a failed factorisation, but runs
+    none: `info()["factorizations"]` does not count it."""
+
+    _model_entry = "fpsq_band_nlp_create_fn"
+
+    def _model_extra(self, nlp_data):
+        return (np.ascontiguousarray(nlp_data.codes, dtype=np.uint8),)
+
+    def objgrad(self, x, gx=None, ys=None, gs=None, xk=None):
+        fx = C.c_double()
+        where = C.c_int32(0)
+        self._order(x, gx, ys, gs, xk)
+        rc = self._check(self._lib.fpsq_band_nlp_objgrad(self._h, self._q, _lib.ptr(x), self.sigma, self.rho, self.eta,
+                                                         self.delta, _lib.ptr(xk), C.byref(fx), _lib.ptr(gx), _lib.ptr(ys),
+                                                         _lib.ptr(gs), C.byref(where)))
+        if rc and where.value == -1:
+            import warnings
+            warnings.warn("DeviceBandSepFuncNLP: J(x) holds a non-finite value (nothing was factorised or evaluated)")
+            return float("nan"), rc
+        self.factorizations += 1
+        if rc:
+            import warnings
+            warnings.warn("DeviceBandSepFuncNLP: J J' + delta I is not positive definite (no valid factorisation)")
+            return float("nan"), rc
+        return fx.value, 0
+
+
+class DeviceArrowBandSepFuncNLP(DeviceBandSepFuncNLP):
+    """DeviceBandSepFuncNLP on an ARROW band (DeviceArrowBandSepQuadNLP's handle): at most `border` long constraint rows and at
+    most `cols` long columns (both 0 .. 16) stay out of the band; function codes may sit on the entries of border rows and of
+    long columns like on any other.  The handle comes from `fpsq_band_create_arrow`; with every code 0 the model is
+    DeviceArrowBandSepQuadNLP's, with `border=0, cols=0` DeviceBandSepFuncNLP's, bit for bit."""
+
+    _create_entry = "fpsq_band_create_arrow"
+
+    def __init__(self, nlp_data, border=16, cols=16, **kwargs):
+        self._limits = (int(border), int(cols))
+        super().__init__(nlp_data, **kwargs)
+
+
 def rccl_unique_id() -> bytes:
     """128-byte RCCL id (call on rank 0, broadcast, pass to every rank's DeviceEqQP(comm=("rccl", ...)))."""
     lib = _lib.load()

@@ -303,6 +303,40 @@ class SepQuadConModel(EqQPModel):
     def ghjvprod(self, x, g, v): return self._H @ (np.asarray(g) * np.asarray(v))
 
 
+class SepFuncConModel(SepQuadConModel):
+    """Host view of problems.SepFuncNLP: c_i(x) = sum_j (A_ij x_j + H_ij phi_kij(x_j)) - b_i with phi from problems.FN_TABLE
+    by the entry's code.  J(x)_ij = A_ij + H_ij phi'(x_j), sum_i y_i Hess c_i = diag(G(x)'y) and
+    ghjvprod(x, g, v) = G(x) (g .* v) with G(x)_ij = H_ij phi''(x_j).  With every code 0 it is SepQuadConModel."""
+
+    def __init__(self, data):
+        super().__init__(data)
+        self.codes = np.ascontiguousarray(data.codes, dtype=np.uint8)
+        self.meta.name = data.qp.name + "-sepfunc"
+
+    def _at(self, x, order):
+        """H_ij times the order-th derivative of the entry's function at x_j, as a CSR matrix on the pattern"""
+        import scipy.sparse as sp
+        from .problems import fn_apply
+
+        qp = self.qp
+        vals = self.hvals * fn_apply(self.codes, np.asarray(x, float)[qp.colind], order)
+        return sp.csr_matrix((vals, qp.colind, qp.rowptr), shape=(qp.m, qp.n))
+
+    def cons(self, x):
+        x = np.asarray(x, float)
+        return self._A @ x + np.asarray(self._at(x, 0).sum(axis=1)).ravel() - self.b
+
+    def jac_coord(self, x):
+        from .problems import fn_apply
+
+        return self.qp.vals + self.hvals * fn_apply(self.codes, np.asarray(x, float)[self.qp.colind], 1)
+
+    def hprod(self, x, y, v, obj_weight=1.0):
+        return obj_weight * self.qp.qdiag * np.asarray(v) + (self._at(x, 2).T @ y) * np.asarray(v)
+
+    def ghjvprod(self, x, g, v): return self._at(x, 2) @ (np.asarray(g) * np.asarray(v))
+
+
 class CoupledQuadConModel(SepQuadConModel):
     """Host view of problems.CoupledQuadNLP: SepQuadConModel plus the coupling terms w_t x_jt x_kt in c_trow.  J(x) gains
     w_t x_kt at (row, jt) and w_t x_jt at (row, kt) -- entries of the pattern --, sum_i y_i Hess c_i = diag(H'y) + Wo(y) with

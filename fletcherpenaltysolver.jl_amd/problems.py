@@ -231,6 +231,94 @@ def with_quadratic_constraints(qp: EqQP, curv: float = 0.1, seed: int = 0) -> Se
     return SepQuadNLP(qp, np.ascontiguousarray(hvals, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64))
 
 
+# the function table of include/fpsq.h (FPSQ_FN_*): code -> (phi, phi', phi'') as numpy callables
+FN_HALFSQ, FN_CUBE6, FN_SIN, FN_COS, FN_EXP, FN_TANH = range(6)
+FN_TABLE = (
+    (lambda x: 0.5 * x * x, lambda x: x, lambda x: np.ones_like(x)),
+    (lambda x: x * x * x / 6.0, lambda x: 0.5 * x * x, lambda x: x),
+    (np.sin, np.cos, lambda x: -np.sin(x)),
+    (np.cos, lambda x: -np.sin(x), lambda x: -np.cos(x)),
+    (np.exp, np.exp, np.exp),
+    (np.tanh, lambda x: 1.0 - np.tanh(x) ** 2, lambda x: -2.0 * np.tanh(x) * (1.0 - np.tanh(x) ** 2)),
+)
+
+
+def fn_apply(codes: np.ndarray, x: np.ndarray, order: int) -> np.ndarray:
+    """the order-th derivative (0, 1, 2) of phi_codes[k] at x[k], entry by entry"""
+    x = np.asarray(x, float)
+    out = np.empty_like(x)
+    for c, fns in enumerate(FN_TABLE):
+        sel = codes == c
+        if sel.any():
+            out[sel] = fns[order](x[sel])
+    return out
+
+
+@dataclass
+class SepFuncNLP(SepQuadNLP):
+    """A SepQuadNLP whose curvature entries carry a FUNCTION each: c_i(x) = sum_j (A_ij x_j + H_ij phi_kij(x_j)) - b_i with
+    phi from FN_TABLE by the code byte of the entry (code 0, 1/2 x^2, is SepQuadNLP's term), so J(x)_ij = A_ij + H_ij phi'(x_j)
+    keeps the pattern (nlpmodels.SepFuncConModel, include/fpsq.h fpsq_band_nlp_create_fn)."""
+
+    codes: np.ndarray = None  # uint8, in the CSR order of qp.vals
+
+
+def _sepfunc(qp, hvals, codes) -> SepFuncNLP:
+    """the model with b set so that xhat is feasible"""
+    import scipy.sparse as sp
+
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    assert codes.shape == qp.vals.shape and (codes.size == 0 or int(codes.max()) < len(FN_TABLE))
+    H = sp.csr_matrix((hvals * fn_apply(codes, qp.xhat[qp.colind], 0), qp.colind, qp.rowptr), shape=(qp.m, qp.n))
+    b = qp.scipy_csr() @ qp.xhat + np.asarray(H.sum(axis=1)).ravel()
+    return SepFuncNLP(qp, np.ascontiguousarray(hvals, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64), codes)
+
+
+def with_function_constraints(qp: EqQP, curv: float = 0.1, seed: int = 0, codes=None) -> SepFuncNLP:
+    """`with_quadratic_constraints(qp, curv, seed)` (the same draw of hvals) with a function code on every entry: uniform over
+    the table from numpy's default_rng(seed) (a generator of its own, so the hvals do not move) unless `codes` is given.  b is
+    set so that xhat stays feasible."""
+    hvals = with_quadratic_constraints(qp, curv, seed).hvals
+    if codes is None:
+        codes = np.random.default_rng(seed).integers(0, len(FN_TABLE), qp.vals.size)
+    return _sepfunc(qp, hvals, codes)
+
+
+def pendulum_like(N=2000, tau=0.05, alpha=0.1, seed=1234) -> SepFuncNLP:
+    """A controlled pendulum theta'' = -sin theta + u by explicit Euler steps of length tau: (theta_k, omega_k, u_k)
+    interleaved for k = 0 .. N - 1, then the final (theta_N, omega_N): n = 3 N + 2, m = 2 N, a band of width 5.  Rows
+        2k:      theta_{k+1} - theta_k - tau omega_k = 0,
+        2k + 1:  omega_{k+1} - omega_k + tau sin theta_k - tau u_k = 0;
+    the sine sits on the entry (2k + 1, theta_k) with A_ij = 0 stored EXPLICITLY, H_ij = tau and code FN_SIN; every other entry
+    has H_ij = 0 and code 0.  xhat is the trajectory simulated from theta_0 = 0.3, omega_0 = 0 under u_k = 1/2 sin(0.1 k), so it
+    is feasible with b = 0 up to rounding (b is set from it all the same).  Objective: q = 1 on the states, alpha on the
+    controls, d = -1/2 q .* xhat.  x = xhat + 0.1 (2u - 1) from the counter-based generator."""
+    n, m = 3 * N + 2, 2 * N
+    k = np.arange(N, dtype=np.int64)
+    th, om, u = 3 * k, 3 * k + 1, 3 * k + 2
+    # row 2k: (theta_k, omega_k, theta_{k+1}); row 2k + 1: (theta_k, omega_k, u_k, omega_{k+1})
+    rowptr = np.concatenate([[0], np.cumsum(np.tile([3, 4], N))]).astype(np.int64)
+    colind = np.stack([th, om, th + 3, th, om, u, om + 3], axis=1).ravel()
+    vals = np.tile(np.array([-1.0, -tau, 1.0, 0.0, -1.0, -tau, 1.0]), N)
+    hvals = np.tile(np.array([0.0, 0.0, 0.0, tau, 0.0, 0.0, 0.0]), N)
+    codes = np.tile(np.array([0, 0, 0, FN_SIN, 0, 0, 0], dtype=np.uint8), N)
+    xhat = np.zeros(n)
+    theta, omega = 0.3, 0.0
+    for i in range(N):
+        ui = 0.5 * np.sin(0.1 * i)
+        xhat[3 * i: 3 * i + 3] = theta, omega, ui
+        theta, omega = theta + tau * omega, omega - tau * np.sin(theta) + tau * ui
+    xhat[3 * N:] = theta, omega
+    idx = np.arange(n, dtype=np.int64)
+    ctrl = (idx % 3 == 2) & (idx < 3 * N)
+    qdiag = np.where(ctrl, alpha, 1.0)
+    d = -0.5 * qdiag * xhat
+    x = xhat + 0.1 * (2.0 * uniform01(seed, idx, 4) - 1.0)
+    qp = EqQP(f"pendulum-N{N}", n, m, rowptr.astype(np.int32), colind.astype(np.int32), vals, qdiag, d, np.zeros(m), x,
+              xhat)   # (qp.b is the LINEAR constraints' and is not used)
+    return _sepfunc(qp, hvals, codes)
+
+
 @dataclass
 class CoupledQuadNLP(SepQuadNLP):
     """A SepQuadNLP plus coupling terms t = (t_row, t_j, t_k, t_w), each adding t_w x_tj x_tk to c_trow (0-based, t_j != t_k):

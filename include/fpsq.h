@@ -654,12 +654,46 @@ int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
  *                         that handle: 4 or 5), Val(1) 10 (7).  FPSQ_BAND_NLP_LONG_ROWS=0, read at create, leaves the long rows
  *                         inside S for the lane-group kernels (one launch fewer per objgrad, two per hprod): the independent form
  *                         the split one is measured and cross-checked against (profiles/band_coupled_arrow_nlp.md).
+ *   fpsq_band_nlp_create_fn  the model with ELEMENTWISE FUNCTION TERMS: one code byte per entry (fn_codes, in the order of
+ *                         a_vals; host or device pointer, copied) names phi from the table FPSQ_FN_* below, and
+ *                           c_i(x)  = sum_j (A_ij x_j + H_ij phi_kij(x_j)) - b_i,
+ *                           J(x)_ij = A_ij + H_ij phi'(x_j),     sum_i y_i Hess c_i = diag(G(x)'y),  G(x)_ij = H_ij phi''(x_j),
+ *                           ghjvprod(x, g, v) = G(x) (g .* v):
+ *                         sin theta of a rotating body, a reaction rate exp, a cubic spring, a saturating tanh.  J(x) keeps the
+ *                         pattern, so the handle, its orderings and the factorisation are untouched.  Handles as
+ *                         fpsq_band_nlp_create_arrow takes them (plain, reordered, two-chain, border rows, long columns, arrow;
+ *                         a fpsq_band_create_coo* handle: FPSQ_ERR_STATE, its message under this entry's name).  A code >= 6
+ *                         gives FPSQ_ERR_ARG and a message that names the first such entry.  With fn_codes NULL or every code 0
+ *                         (phi = 1/2 x^2) the model IS fpsq_band_nlp_create_arrow's on that handle: the same launches, the same
+ *                         bits.  The entries above take the model with the same state rules, soft codes and formulas, H' read
+ *                         as G(x)': the curvature coefficient is an array that every objgrad rewrites next to J(x) (both in
+ *                         the stored and in the transposed order, by the same device function: the same bits), and an hprod
+ *                         runs on the G of the last successful objgrad, which the model keeps.  c(x) inside an objgrad is
+ *                         sum_k (J_k x_c - rem_k) - b with the remainder rem = H (phi'(x) x - phi(x)) written next to J;
+ *                         fpsq_band_nlp_cons evaluates phi itself.  The model adds NO launch to any evaluation -- the two value
+ *                         launches of an objgrad are replaced by their function forms --, one 4-byte readback per objgrad and
+ *                         nnz + t_nnz + nnz doubles.  NON-FINITE J(x) (exp overflows above 709; every entry is evaluated
+ *                         whatever its H_ij): the value launch raises a word the objgrad reads BEFORE it factorises; it then
+ *                         returns the soft code 1 with *fx = nan, *info = -1 (no pivot row), nothing factorised, nothing
+ *                         evaluated and no output written -- what a failed factorisation returns, and the state an hprod
+ *                         refuses.  Function terms TOGETHER with coupling terms are not offered.
  * Destroy a model before the handle it was created on. */
+enum { /* phi, phi', phi'' of a function code (one byte per entry) */
+  FPSQ_FN_HALFSQ = 0, /* 1/2 x^2,  x,         1                  */
+  FPSQ_FN_CUBE6 = 1,  /* x^3 / 6,  1/2 x^2,   x                  */
+  FPSQ_FN_SIN = 2,    /* sin x,    cos x,     -sin x             */
+  FPSQ_FN_COS = 3,    /* cos x,    -sin x,    -cos x             */
+  FPSQ_FN_EXP = 4,    /* exp x,    exp x,     exp x              */
+  FPSQ_FN_TANH = 5,   /* t = tanh x,  1 - t^2,  -2 t (1 - t^2)   */
+  FPSQ_FN_COUNT = 6
+};
 typedef struct fpsq_band_nlp_s *fpsq_band_nlp;
 int fpsq_band_nlp_create(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
                          const double *h_vals, fpsq_band_nlp *out);
 int fpsq_band_nlp_create_arrow(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
                                const double *h_vals, fpsq_band_nlp *out);
+int fpsq_band_nlp_create_fn(fpsq_band b, const double *qdiag, const double *d, const double *bvec, const double *a_vals,
+                            const double *h_vals, const uint8_t *fn_codes, fpsq_band_nlp *out);
 int fpsq_band_nlp_create_coupled(fpsq_band b, const double *qdiag, const double *d, const double *bvec,
                                  const double *a_vals, const double *h_vals,
                                  int64_t nterms, const int32_t *t_row, const int32_t *t_j, const int32_t *t_k,

@@ -17,6 +17,9 @@ and the bits of fx.  A line belongs to one evaluation, so a differing line names
   coupled-arrow  DeviceArrowBandCoupledQuadNLP  every case of tests/coupled_arrow_cases.py.  NOT among the defaults: a build from
                                           before fpsq_band_nlp_create_coupled_arrow lacks the entry (name it in --models to compare
                                           two builds that have it)
+  fn          DeviceBandSepFuncNLP        the function model (tests/sepfunc_ref.py fn_data) on every case of
+                                          tests/lane_group_cases.py, and DeviceArrowBandSepFuncNLP on the arrow shapes.  NOT among
+                                          the defaults: a build from before fpsq_band_nlp_create_fn lacks the entry
 Accuracy is the tests' business."""
 import argparse
 import hashlib
@@ -64,10 +67,17 @@ if args.other_lib:   # this process never opens the GPU: each build evaluates in
 
 import fps_amd  # noqa: E402,F401
 from fps_amd import _lib, problems  # noqa: E402
+from fps_amd import device_qp  # noqa: E402
 from fps_amd.device_qp import (DeviceArrowBandCoupledQuadNLP, DeviceArrowBandSepQuadNLP, DeviceBandCoupledQuadNLP,  # noqa: E402
                                DeviceBandSepQuadNLP)
 import coupled_cases as cc  # noqa: E402
 import lane_group_cases as L  # noqa: E402
+
+if os.environ.get("FPSQ_LIB_PATH"):   # another build may predate entries this tree declares: bind the ones it has
+    import ctypes
+
+    _have = ctypes.CDLL(_lib.LIB_PATH)
+    _lib.SYMBOLS = [s for s in _lib.SYMBOLS if hasattr(_have, s[0])]
 
 SE = float(np.sqrt(np.finfo(float).eps))
 SIGMA, RHO, ETA = 1e3, 1.0, 0.5
@@ -120,5 +130,15 @@ for model in args.models.split(","):
         for name in ca.NAMES:
             border, cols = ca.limits(name)
             evaluate(model, name, DeviceArrowBandCoupledQuadNLP(ca.problem(name)[0], border=border, cols=cols, **kw))
+    elif model == "fn":
+        import sepfunc_ref as F
+        import test_gpu_band_arrow_nlp as T
+
+        for name in L.NAMES:
+            evaluate(model, name, device_qp.DeviceBandSepFuncNLP(F.fn_data(name), **kw))
+        for name in T.CASES:
+            border, cols = T.CASES[name][2]
+            data = F.fn_data_of(T.CASES[name][0]()[0])
+            evaluate(model, name, device_qp.DeviceArrowBandSepFuncNLP(data, border=border, cols=cols, **kw))
     else:
         raise SystemExit(f"unknown model {model}")
