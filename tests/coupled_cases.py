@@ -25,8 +25,9 @@ PAIRS = 2 terms per row and CURV = 0.3 (tests/test_gpu_band_nlp.py's curvature) 
 
 STRIDE.  n = 720001, m = 360000, nnz = 1080000, lgA = 2, lgT = 1, lgR = 1: the row kernels walk 2813 (rows of A, 128 a tile) and
 2813 (rows of A' and of S, 256 a tile) tiles against kBqMaxGrid = 2048, and the per-entry kernels 4219 (k_bcn_vals, 256 entries a
-workgroup) against 4096; k_bcn_assemble's 2813 workgroups stay under 4096: ITS second trip no test reaches (it would take
-nnz(S) > 1048576, i.e. N > 524288)."""
+workgroup) against 4096; k_bcn_assemble's 2813 workgroups stay under 4096: its second trip takes nnz(S) > 1048576, which with
+one term per row would be N > 524288, and which a dense term rule reaches at n = 2048 -- the case assemble-stride of
+tests/coupled_lane_cases.py (tests/test_gpu_coupled_lane_groups.py)."""
 import dataclasses
 import functools
 

@@ -66,24 +66,32 @@ ragged(-shuffled), 64 both-64(-shuffled) / stride;  lgR: m-near-n with the half-
     k_bn_epilogue_h1      lgT  hprod Val(1)                                         all; stride
     k_bn_hgv              lgA  hprod Val(1)                                         all; stride
     k_bn_jtz              lgT  hprod Val(1)                                         all; stride
+  fpsq_band_nlp.hip.h, the model with function terms: three of the dispatches above launch a function form from their `else`
+  branch; the other sites are shared as they are.  "fn" = part 1 of tests/test_gpu_band_fn_nlp.py, which runs every case of
+  this table (all seven widths on each side) and stride (the second trip).
+    k_bn_cons_fn                    lgA  cons (rows = m)                            fn: all; stride
+    k_bn_tvals_fn                   lgT  objgrad: J(x)' and G(x)' per row           fn: all; stride
+    k_bn_prologue<LG, false, true>  lgA  objgrad (the FN form)                      fn: all; stride
   fpsq_band_nlp.hip.h, the model with coupling terms.  The five kernels with the flag CP are the rows above instantiated as
   k_bn_*<LG, true> (the rows above are <LG, false>); k_bn_jtz and the Val(1) k_bq_prologue site are shared as they are; k_bn_tvals
   is not run (k_bcn_vals, per entry, twice).  "coupled" = the cases of tests/coupled_cases.py, which reach
   lgA 2, 4, 16, 32; lgT 1, 2, 32; lgR 1, 8 and no other width (tests/test_lane_groups_cpu.py recomputes the three sets); second
-  trip of the grid-stride loop: coupled_cases.py STRIDE at 2 / 1 / 1.  The other widths of these instantiations no test runs.
-    k_bn_cons<LG, true>         lgA  cons (rows = m)                                coupled; STRIDE
-    k_bn_prologue<LG, true>     lgA  objgrad                                        coupled; STRIDE
-    k_bn_epilogue<LG, true>     lgT  objgrad                                        coupled; STRIDE
-    k_bcn_finish                lgR  objgrad with gx: the rows of S                 coupled; STRIDE
-    k_bcn_hcv                   lgR  hprod Val(2), rho > 0                          coupled; STRIDE
-    k_bq_pack_sq                lgR  hprod Val(1) (<LG, true>; Val(2): bq_launches) coupled; STRIDE
-    k_bn_epilogue_h1<LG, true>  lgT  hprod Val(1)                                   coupled; STRIDE
-    k_bcn_finish_h1             lgR  hprod Val(1): the rows of S                    coupled; STRIDE
-    k_bn_hgv<LG, true>          lgA  hprod Val(1)                                   coupled; STRIDE
+  trip of the grid-stride loop: coupled_cases.py STRIDE at 2 / 1 / 1.  "lanes" = the cases of tests/coupled_lane_cases.py (a
+  denser term rule on the shapes of this table), which reach every width of lgA, of lgT and of lgR
+  (tests/test_coupled_lane_groups_cpu.py recomputes the three sets; tests/test_gpu_coupled_lane_groups.py runs them).
+    k_bn_cons<LG, true>         lgA  cons (rows = m)                                coupled; STRIDE; lanes: all
+    k_bn_prologue<LG, true>     lgA  objgrad                                        coupled; STRIDE; lanes: all
+    k_bn_epilogue<LG, true>     lgT  objgrad                                        coupled; STRIDE; lanes: all
+    k_bcn_finish                lgR  objgrad with gx: the rows of S                 coupled; STRIDE; lanes: all
+    k_bcn_hcv                   lgR  hprod Val(2), rho > 0                          coupled; STRIDE; lanes: all
+    k_bq_pack_sq                lgR  hprod Val(1) (<LG, true>; Val(2): bq_launches) coupled; STRIDE; lanes: all
+    k_bn_epilogue_h1<LG, true>  lgT  hprod Val(1)                                   coupled; STRIDE; lanes: all
+    k_bcn_finish_h1             lgR  hprod Val(1): the rows of S                    coupled; STRIDE; lanes: all
+    k_bn_hgv<LG, true>          lgA  hprod Val(1)                                   coupled; STRIDE; lanes: all
   not under WITH_LANE_GROUP but capped (one helper, flat_grid): k_bn_vals (objgrad) and the k_gather_d launches of
   fpsq_band_nlp_create (the handle of stride is reordered into two chains, so both gathers run): 4150 blocks of entries against
-  4096 on stride; with coupling terms k_bcn_vals (4219 blocks on STRIDE) and k_bcn_assemble (2813: its second trip no test
-  reaches).
+  4096 on stride; with coupling terms k_bcn_vals (4219 blocks on STRIDE) and k_bcn_assemble (2813 on STRIDE; 6501 on the case
+  assemble-stride of tests/coupled_lane_cases.py, which takes it through its second trip).
 
 YARDSTICKS.  exact_linear: tests/sparse_hessian_ref.py (one LU of K = [I A'; A -delta I], kept), which on a diagonal Hessian
 evaluates the formulae of oracle.exact_qp_objgrad / exact_qp_hprod.  exact_nonlinear: tests/sepquad_ref.py with its three

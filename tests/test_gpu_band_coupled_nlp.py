@@ -7,7 +7,8 @@ bar tells the two models apart.  The cases: tests/coupled_cases.py.
 
 Second trips of the grid-stride loops: the case `stride` takes k_bcn_vals (both launches), k_bn_prologue<LG, true>,
 k_bn_epilogue<LG, true>, k_bcn_finish, k_bcn_hcv, k_bn_epilogue_h1<LG, true>, k_bcn_finish_h1, k_bn_hgv<LG, true> and
-k_bn_cons<LG, true> through theirs; k_bcn_assemble's no test reaches (coupled_cases.py STRIDE)."""
+k_bn_cons<LG, true> through theirs; k_bcn_assemble's takes nnz(S) > 1048576 (with one term per row N > 524288) and is reached by
+the case assemble-stride of tests/test_gpu_coupled_lane_groups.py, which also runs these kernels at every lane-group width."""
 import ctypes as C
 import dataclasses
 import os

@@ -137,15 +137,34 @@ def test_the_symbolic_phase_takes_every_case(name):
 
 
 def test_the_site_table_names_every_dispatch_of_the_band_unit():
-    """every kernel launched under WITH_LANE_GROUP in fpsq_band.hip and fpsq_band_nlp.hip.h has a row in the docstring table"""
-    sites = []
+    """every kernel launched under WITH_LANE_GROUP in fpsq_band.hip and fpsq_band_nlp.hip.h has a row in the docstring table:
+    EVERY kernel named inside the balanced parentheses of an invocation (a dispatch may launch one kernel or another: the
+    function forms sit in the `else` branches of the separable model's dispatches), not the first alone.  Where one invocation
+    names the same kernel twice, the second instantiation needs a row that spells its template arguments."""
+    sites, first_only = [], []
     for f in ("fpsq_band.hip", "fpsq_band_nlp.hip.h"):
         src = open(os.path.join(CSRC, f)).read()
-        sites += re.findall(r"WITH_LANE_GROUP\((?:qp->|lin\.)?(\w+),.*?\(?(k_\w+)<", src, flags=re.S)
-    assert len(sites) == 30   # (18 in fpsq_band.hip, 12 in fpsq_band_nlp.hip.h, the model with coupling terms included)
-    assert {lg for lg, _ in sites} == {"lgA", "lgT", "lgR", "lg"}
-    for _, kernel in sites:
+        first_only += re.findall(r"WITH_LANE_GROUP\((?:qp->|lin\.)?(\w+),.*?\(?(k_\w+)<", src, flags=re.S)
+        for inv in re.finditer(r"WITH_LANE_GROUP\(", src):
+            end, depth = inv.end(), 1
+            while depth:
+                depth += {"(": 1, ")": -1}.get(src[end], 0)
+                end += 1
+            body = src[inv.end():end - 1]
+            lg = re.match(r"\s*(?:qp->|lin\.)?(\w+),", body).group(1)
+            named = re.findall(r"\b(k_\w+)\s*(<[^>]*>|(?=\)))", body)
+            assert named, body
+            for i, (kernel, targs) in enumerate(named):
+                sites.append((lg, kernel, re.sub(r"\s+", " ", targs) if kernel in [k for k, _ in named[:i]] else None))
+    assert len(first_only) == 30 and set(first_only) <= {(lg, kernel) for lg, kernel, _ in sites}   # what the first name gave
+    assert len(sites) == 33   # (18 in fpsq_band.hip, 15 in fpsq_band_nlp.hip.h: 12 dispatches, three with a function form)
+    assert {lg for lg, _, _ in sites} == {"lgA", "lgT", "lgR", "lg"}
+    for _, kernel, targs in sites:
         assert re.search(rf"^\s+{kernel}\b", L.__doc__, flags=re.M), kernel
+        if targs is not None:
+            assert re.search(rf"^\s+{re.escape(kernel + targs)}\s", L.__doc__, flags=re.M), kernel + targs
+    assert {(k, t) for _, k, t in sites if k.endswith("_fn") or t} == {("k_bn_cons_fn", None), ("k_bn_tvals_fn", None),
+                                                                         ("k_bn_prologue", "<LG, false, true>")}
 
 
 def test_the_widths_the_coupled_cases_reach():
