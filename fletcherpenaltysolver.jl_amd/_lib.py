@@ -149,6 +149,7 @@ SYMBOLS = [
     ("fpsq_band_nlp_create_fn", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, _VP, C.POINTER(_VP)]),
     ("fpsq_band_nlp_create_coupled", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.c_int64, _VP, _VP, _VP, _DP, C.POINTER(_VP)]),
     ("fpsq_band_nlp_create_coupled_arrow", C.c_int, [_VP, _DP, _DP, _DP, _DP, _DP, C.c_int64, _VP, _VP, _VP, _DP, C.POINTER(_VP)]),
+    ("fpsq_band_nlp_set_objective_terms", C.c_int, [_VP, _VP, _DP, _VP]),
     ("fpsq_band_nlp_destroy", C.c_int, [_VP]),
     ("fpsq_band_nlp_objgrad", C.c_int, [_VP, _VP, _DP, _D, _D, _D, _D, _DP, C.POINTER(C.c_double), _DP, _DP, _DP,
                                         C.POINTER(C.c_int32)]),

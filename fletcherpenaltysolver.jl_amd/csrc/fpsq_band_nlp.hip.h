@@ -180,6 +180,45 @@ __global__ __launch_bounds__(256) void k_bn_tvals_fn(const int32_t* __restrict__
   }
 }
 
+// ---- FUNCTION TERMS IN THE OBJECTIVE (fpsq_band_nlp_set_objective_terms): f(x) = 1/2 x' diag(q) x + d'x + sum_j w_j psi_kj(x_j),
+// psi from the same table by one code byte per VARIABLE.  grad f = q x + d + w psi'(x) and Hess f = diag(q + w psi''(x)), and
+// q and d enter an objgrad only through k_bq_pack<false>, k_bn_epilogue and k_bn_lc_epilogue (the Hessian products read qe, hc
+// and gs): this kernel rewrites two EFFECTIVE vectors per objgrad,
+//   qx_j = q_j + w_j psi''(x_j),   de_j = d_j + w_j (psi'(x_j) - psi''(x_j) x_j),   so that qx_j x_j + de_j = grad f(x)_j,
+// and those kernels take (qx, de) where they take (q, d), unchanged.  part[blk] = this workgroup's slice of f, over the chunk
+// of the prologue's objective slice (contiguous, ceil(n / grid) entries), summed in a fixed order; k_bq_phi_sq finishes fx from
+// it.  An entry with w_j = 0 is not evaluated (qx_j = q_j, de_j = d_j: exp at 800 under w_j = 0 is harmless).  A non-finite
+// w psi, w psi' or w psi'' raises bit 1 of *flag (k_bn_vals_fn stores 1 there, and has run before this launch); the driver
+// reads the word before it factorises
+__global__ __launch_bounds__(256) void k_bn_objfn(const double* __restrict__ x, const double* __restrict__ q,
+                                                  const double* __restrict__ d, const double* __restrict__ w,
+                                                  const uint8_t* __restrict__ code, double* __restrict__ qx,
+                                                  double* __restrict__ de, double* __restrict__ part, int32_t* __restrict__ flag,
+                                                  int n) {
+  __shared__ double sh[4];
+  double red[1] = {0.0};
+  const int64_t chunk = ((int64_t)n + gridDim.x - 1) / gridDim.x;
+  const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+  for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
+    const double xv = x[j], qv = q[j], dv = d[j], wv = w[j];
+    double f = xv * (0.5 * qv * xv + dv), qo = qv, eo = dv;
+    if (wv != 0.0) {
+      double p0, p1, p2;
+      bn_fn_eval(code[j], xv, p0, p1, p2);
+      const double t0 = wv * p0, t1 = wv * p1, t2 = wv * p2;
+      if (!(isfinite(t0) && isfinite(t1) && isfinite(t2))) atomicOr(flag, 2);
+      f += t0;
+      qo = qv + t2;
+      eo = dv + wv * (p1 - p2 * xv);
+    }
+    qx[j] = qo;
+    de[j] = eo;
+    red[0] += f;
+  }
+  bq_block_sum(red, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
 // With coupling terms: vals[k] = a[k] + h[k] x[col[k]] + sum_u pw[u] x[pcol[u]] over the entries of ONE CSR and their partner
 // lists: launched on the stored structure (col = colind) and on the transposed one (col = the entry's own column, its lists in
 // the same order), so both value arrays get the same bits
@@ -768,6 +807,14 @@ struct fpsq_band_nlp_s {
   int32_t* flag = nullptr;
   const double* curv() const { return fn ? g : h; }
   const double* tcurv() const { return fn ? tg : th; }
+  // fpsq_band_nlp_set_objective_terms: the weights and code bytes per variable, the effective vectors and the partials of f
+  // that k_bn_objfn rewrites per objgrad (gridP doubles); `objfn` is off until terms are set and after they are removed, and
+  // then every launch takes q and d themselves.  `flag` is allocated with the first terms where the model has none
+  bool objfn = false;
+  double *ow = nullptr, *qx = nullptr, *de = nullptr, *partO = nullptr;
+  uint8_t* ocode = nullptr;
+  const double* oq() const { return objfn ? qx : q; }
+  const double* od() const { return objfn ? de : d; }
   double *partP = nullptr, *partE = nullptr;
   fpsq_band_qp_s lin;
   uint64_t fact_gen = 0;   // the handle's factorisation count when that objgrad ended
@@ -1055,6 +1102,52 @@ int fpsq_band_nlp_create_coupled_arrow(fpsq_band b, const double* qdiag, const d
   return FPSQ_OK;
 }
 
+int fpsq_band_nlp_set_objective_terms(fpsq_band b, fpsq_band_nlp nlp, const double* w, const uint8_t* codes) {
+  static const char* entry = "band_nlp_set_objective_terms";
+  if (!b || !nlp) return FPSQ_ERR_ARG;
+  if (nlp->b != b) {
+    b->err = std::string(entry) + ": the model was created on another handle";
+    return FPSQ_ERR_ARG;
+  }
+  nlp->evaluated = false;  // (qe, hc and gs are those of another objective: the next objgrad fixes the point again)
+  if (!w) {                // without terms the model is the one it was: the launches take q and d themselves
+    nlp->objfn = false;
+    return FPSQ_OK;
+  }
+  hipSetDevice(b->device);
+  if (int rc = wait_input(b)) return rc;
+  // (device-resident arguments are complete, and nothing of an earlier evaluation reads the arrays below any more)
+  CHK(b, hipStreamSynchronize(b->stream));
+  const size_t n = (size_t)b->n;
+  std::vector<double> wh(n);
+  std::vector<uint8_t> ch(n, 0);
+  CHK(b, hipMemcpy(wh.data(), w, n * 8, hipMemcpyDefault));
+  if (codes) CHK(b, hipMemcpy(ch.data(), codes, n, hipMemcpyDefault));
+  for (size_t j = 0; j < n; ++j)
+    if (wh[j] != 0.0 && ch[j] >= FPSQ_FN_COUNT) {
+      b->err = std::string(entry) + ": codes[" + std::to_string(j) + "] = " + std::to_string((int)ch[j]) +
+               " is not a function code (0 .. " + std::to_string(FPSQ_FN_COUNT - 1) + ") and w[" + std::to_string(j) + "] is not 0";
+      return FPSQ_ERR_ARG;
+    }
+  const auto H2D = hipMemcpyHostToDevice;
+  bool ok = true;
+  if (!nlp->partO)  // (the last of the five: a call that failed half-way allocates again)
+    ok = qp_buffers(nlp, {{(void**)&nlp->ow, std::max<size_t>(n, 1) * 8, nullptr, H2D},
+                          {(void**)&nlp->qx, std::max<size_t>(n, 1) * 8, nullptr, H2D},
+                          {(void**)&nlp->de, std::max<size_t>(n, 1) * 8, nullptr, H2D},
+                          {(void**)&nlp->ocode, std::max<size_t>(n, 1), nullptr, H2D},
+                          {(void**)&nlp->partO, (size_t)nlp->lin.gridP * 8, nullptr, H2D}});
+  if (ok && !nlp->flag) ok = qp_buffers(nlp, {{(void**)&nlp->flag, 8, nullptr, H2D}}) && hipMemset(nlp->flag, 0, 8) == hipSuccess;
+  ok = ok && hipMemcpy(nlp->ow, wh.data(), n * 8, H2D) == hipSuccess && hipMemcpy(nlp->ocode, ch.data(), n, H2D) == hipSuccess;
+  if (!ok) {
+    nlp->objfn = false;
+    b->err = std::string(entry) + ": cannot allocate or fill the objective terms";
+    return FPSQ_ERR_HIP;
+  }
+  nlp->objfn = true;
+  return FPSQ_OK;
+}
+
 int fpsq_band_nlp_cons(fpsq_band b, fpsq_band_nlp nlp, const double* x, double* c) {
   if (!b || !nlp || nlp->b != b || !x || !c) return FPSQ_ERR_ARG;
   hipSetDevice(b->device);
@@ -1114,17 +1207,27 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
                                             nlp->tcode, ax.tile(), b->t_vals, nlp->tg, n))
     if (b->fb_nnz > 0)  // (long columns and k_band_form: the values of the other columns alone, as fpsq_band_factorize)
       hipLaunchKernelGGL(k_gather_d, flat_grid(b->fb_nnz), dim3(256), 0, s, b->vals, b->fb_perm, b->fb_vals, b->fb_nnz);
-    if (nlp->fn) {  // a non-finite J(x) must not reach the factorisation: what a failed one returns, before one is enqueued
-      int32_t* raised = reinterpret_cast<int32_t*>(b->scal_host + 7);  // (pinned; the scalars of a call end at [4])
-      CHK(b, hipMemcpyAsync(raised, nlp->flag, 4, hipMemcpyDeviceToHost, s));
-      CHK(b, hipStreamSynchronize(s));
-      if (*raised) {
-        CHK(b, hipMemsetAsync(nlp->flag, 0, 4, s));
-        b->err = "band_nlp_objgrad: J(x) holds a non-finite value (nothing was factorised or evaluated)";
-        *fx = std::numeric_limits<double>::quiet_NaN();
-        if (info) *info = -1;
-        return 1;
-      }
+  }
+  // with function terms in the objective: the effective (q, d) of this x and the partials of f, behind the value launches
+  const double *oq = nlp->oq(), *od = nlp->od();
+  if (nlp->objfn)
+    hipLaunchKernelGGL(k_bn_objfn, dim3(lin.gridP), dim3(256), 0, s, ax.tile(), nlp->q, nlp->d, nlp->ow, nlp->ocode, nlp->qx, nlp->de,
+                       nlp->partO, nlp->flag, n);
+  if (nlp->fn || nlp->objfn) {  // a non-finite J(x) or objective term must not reach the factorisation: what a failed one
+                                // returns, before one is enqueued (one word: 1 = J(x), 2 = the objective)
+    int32_t* raised = reinterpret_cast<int32_t*>(b->scal_host + 7);  // (pinned; the scalars of a call end at [4])
+    CHK(b, hipMemcpyAsync(raised, nlp->flag, 4, hipMemcpyDeviceToHost, s));
+    CHK(b, hipStreamSynchronize(s));
+    if (*raised) {
+      CHK(b, hipMemsetAsync(nlp->flag, 0, 4, s));
+      b->err = std::string("band_nlp_objgrad: ") +
+               (*raised == 1   ? "J(x) holds"
+                : *raised == 2 ? "the objective's function terms hold"
+                               : "J(x) and the objective's function terms hold") +
+               " a non-finite value (nothing was factorised or evaluated)";
+      *fx = std::numeric_limits<double>::quiet_NaN();
+      if (info) *info = -1;
+      return 1;
     }
   }
   // 2: the numeric factorisation on them
@@ -1134,21 +1237,21 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
   const StagedArg ogx = staged(b, gx, b->o_p1, (size_t)n), ogs = staged(b, gs, b->o_p2, (size_t)n),
                   oys = staged(b, ys, b->o_q1, (size_t)m);
   double* keep = b->cols ? b->bd_keep : b->o_q2;  // (long columns: the operand has virtual rows, as in bq_launches)
-  hipLaunchKernelGGL(k_bq_pack<false>, grid256(n), dim3(256), 0, s, ax.tile(), nlp->q, nlp->d, b->xn, n);
+  hipLaunchKernelGGL(k_bq_pack<false>, grid256(n), dim3(256), 0, s, ax.tile(), oq, od, b->xn, n);
   WITH_LANE_GROUP(lin.lgA, if (!nlp->fn) { WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
       (k_bn_prologue<LG, CP>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, CP ? nlp->a : nlp->h, b->xn,
-      ax.tile(), nlp->q, nlp->d, nlp->bp, b->r2, keep, nlp->partP, m, mpad, n)) } else hipLaunchKernelGGL(
+      ax.tile(), oq, od, nlp->bp, b->r2, keep, nlp->partP, m, mpad, n)) } else hipLaunchKernelGGL(
       (k_bn_prologue<LG, false, true>), dim3(lin.gridP), dim3(256), 0, s, b->rowptr, b->colind, b->vals, nlp->rem, b->xn,
-      ax.tile(), nlp->q, nlp->d, nlp->bp, b->r2, keep, nlp->partP, m, mpad, n))
+      ax.tile(), oq, od, nlp->bp, b->r2, keep, nlp->partP, m, mpad, n))
   if (b->cols) cols_keep<1>(b, keep);
   band_solve(b);
   WITH_LANE_GROUP(lin.lgT, WITH_BOOL(coupled, CP, hipLaunchKernelGGL(
       (k_bn_epilogue<LG, CP>), dim3(lin.gridE), dim3(256), 0, s, b->t_rowptr, b->t_colind, b->t_vals, nlp->tcurv(), b->r2, keep,
-      b->row_perm(), ax.tile(), axk.tile(), nlp->q, nlp->d, sigma, rho, eta, ogx.tile(), ogs.tile(), oys.tile(), nlp->qe, nlp->hc,
+      b->row_perm(), ax.tile(), axk.tile(), oq, od, sigma, rho, eta, ogx.tile(), ogs.tile(), oys.tile(), nlp->qe, nlp->hc,
       nlp->gs, lin.tv, nlp->partE, n, m)))
   if (b->cols)  // the curvature sums at the long columns, whose transposed rows are virtual
     hipLaunchKernelGGL(k_bn_lc_epilogue, dim3(b->cols), dim3(256), 0, s, b->lc_ptr, b->lc_row, b->lc_ent, b->lc_cols, nlp->curv(),
-                       b->r2, keep, ax.tile(), axk.tile(), nlp->q, nlp->gs, sigma, rho, eta, ogx.tile(), nlp->qe, nlp->hc, mpad,
+                       b->r2, keep, ax.tile(), axk.tile(), oq, nlp->gs, sigma, rho, eta, ogx.tile(), nlp->qe, nlp->hc, mpad,
                        b->bc_grid);
   if (coupled) {  // the values of Wo on S, then the rows of S that gx lacks
     hipLaunchKernelGGL(k_bcn_assemble, flat_grid(cp.snz), dim3(256), 0, s, cp.cptr, cp.crow, cp.cw, b->r2, keep, sigma,
@@ -1160,7 +1263,11 @@ int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double* x, doubl
       hipLaunchKernelGGL(k_bq_long_rows<LR_OBJ>, dim3(cp.lr.cols), dim3(256), 0, s, cp.lr, (const double*)nlp->gs,
                          (const double*)lin.tv, (const double*)nullptr, (const double*)nullptr, 0.0, ogx.tile());
   }
-  hipLaunchKernelGGL(k_bq_phi, dim3(1), dim3(256), 0, s, nlp->partP, lin.gridP, nlp->partE, lin.gridE, rho, eta, b->scal);
+  if (nlp->objfn)  // (f from k_bn_objfn's partials; the prologue's own slice, formed from the effective vectors, is not read)
+    hipLaunchKernelGGL(k_bq_phi_sq, dim3(1), dim3(256), 0, s, nlp->partO, lin.gridP, nlp->partP, lin.gridP, nlp->partE, lin.gridE,
+                       rho, eta, b->scal);
+  else
+    hipLaunchKernelGGL(k_bq_phi, dim3(1), dim3(256), 0, s, nlp->partP, lin.gridP, nlp->partE, lin.gridE, rho, eta, b->scal);
   for (const StagedArg* o : {&ogx, &ogs, &oys})
     if (int rc = stage_back(b, *o)) return rc;
   if (int rc = eval_end(b, 5, &b->info.last_solve_ms)) return rc;

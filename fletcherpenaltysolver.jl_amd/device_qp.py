@@ -454,6 +454,7 @@ class DeviceBandSepQuadNLP:
         self.sigma, self.rho, self.delta, self.eta = sigma, rho, float(delta), eta
         self.device = int(device)
         self._h = self._q = None
+        self.obj_w = self.obj_codes = None   # host copies of the objective's function terms (set_objective_terms), or None
         self.factorizations = 0
         self._in_stream = -1
         rp = np.ascontiguousarray(qp.rowptr, dtype=np.int32)
@@ -474,16 +475,41 @@ class DeviceBandSepQuadNLP:
             self._check(getattr(self._lib, self._model_entry)(h, *(a.ctypes.data if isinstance(a, np.ndarray) else a
                                                                    for a in keep), C.byref(q)))
             self._q = q
+            if getattr(nlp_data, "obj_w", None) is not None:   # problems.with_objective_terms
+                self.set_objective_terms(nlp_data.obj_w, getattr(nlp_data, "obj_codes", None))
         except Exception:
             self.close()
             raise
 
     _check = DeviceBandEqQP._check
     _order = DeviceBandEqQP._order
+    _refusal = "a non-finite value in the objective's function terms"   # what an objgrad with info = -1 has met
 
     def _model_extra(self, nlp_data):
         """what `_model_entry` takes between h_vals and the model's address: numpy arrays (kept alive over the call) or scalars"""
         return ()
+
+    def set_objective_terms(self, w, codes=None):
+        """Elementwise function terms in the objective, f += sum_j w_j psi_kj(x_j) (include/fpsq.h
+        fpsq_band_nlp_set_objective_terms): `w` n weights, `codes` n code bytes of the table FPSQ_FN_* (None: every code 0), numpy
+        arrays or torch tensors on the host or the device, copied.  `w=None` removes the terms.  Allowed at any time; the next
+        `hprod` needs a new `objgrad`.  Returns rc."""
+        if w is None:
+            rc = self._check(self._lib.fpsq_band_nlp_set_objective_terms(self._h, self._q, None, None))
+            self.obj_w = self.obj_codes = None
+            return rc
+        if isinstance(w, np.ndarray) or not hasattr(w, "data_ptr"):
+            w = np.ascontiguousarray(w, dtype=np.float64)
+        if codes is not None and (isinstance(codes, np.ndarray) or not hasattr(codes, "data_ptr")):
+            codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        assert w.shape[0] == self.qp.n and (codes is None or codes.shape[0] == self.qp.n)
+        assert str(w.dtype).endswith("float64") and (codes is None or str(codes.dtype).endswith("uint8"))
+        self._order(w, codes)
+        rc = self._check(self._lib.fpsq_band_nlp_set_objective_terms(self._h, self._q, _lib.ptr(w), _lib.ptr(codes)))
+        host = lambda a: a.copy() if isinstance(a, np.ndarray) else a.cpu().numpy()  # noqa: E731
+        self.obj_w = host(w)
+        self.obj_codes = np.zeros(self.qp.n, dtype=np.uint8) if codes is None else host(codes)
+        return rc
 
     def set_delta(self, delta):
         """The delta of the NEXT objgrad's factorisation (an hprod stays on the factor of the last one)."""
@@ -493,14 +519,19 @@ class DeviceBandSepQuadNLP:
         """One objgrad at a fresh x, its factorisation included.  Returns (fx, rc); with rc = 1 (J J' + delta I not positive
         definite and no regularisation) nothing was evaluated: fx is nan and the outputs are untouched."""
         fx = C.c_double()
+        where = C.c_int32(0)
         self._order(x, gx, ys, gs, xk)
         rc = self._check(self._lib.fpsq_band_nlp_objgrad(self._h, self._q, _lib.ptr(x), self.sigma, self.rho, self.eta,
                                                          self.delta, _lib.ptr(xk), C.byref(fx), _lib.ptr(gx), _lib.ptr(ys),
-                                                         _lib.ptr(gs), None))
+                                                         _lib.ptr(gs), C.byref(where)))
+        if rc and where.value == -1:   # refused before the factorisation, which is therefore not counted
+            import warnings
+            warnings.warn(f"{type(self).__name__}: {self._refusal} (nothing was factorised or evaluated)")
+            return float("nan"), rc
         self.factorizations += 1
         if rc:
             import warnings
-            warnings.warn("DeviceBandSepQuadNLP: J J' + delta I is not positive definite (no valid factorisation)")
+            warnings.warn(f"{type(self).__name__}: J J' + delta I is not positive definite (no valid factorisation)")
             return float("nan"), rc
         return fx.value, 0
 
@@ -597,30 +628,13 @@ class DeviceBandSepFuncNLP(DeviceBandSepQuadNLP):
     (1/2 x^2, x^3/6, sin, cos, exp, tanh).  The model comes from `fpsq_band_nlp_create_fn`; every method is the base class's
     and `fps_solve_device` takes the object unchanged.  With every code 0 the model is DeviceBandSepQuadNLP's, bit for bit.
     An objgrad whose J(x) holds a non-finite value (exp above 709) returns (nan, 1) like a failed factorisation, but runs
-    none: `info()["factorizations"]` does not count it."""
+    none: `info()["factorizations"]` does not count it (the base class's objgrad; fpsq_band_last_error says which terms)."""
 
     _model_entry = "fpsq_band_nlp_create_fn"
+    _refusal = "a non-finite value in J(x) or in the objective's function terms"
 
     def _model_extra(self, nlp_data):
         return (np.ascontiguousarray(nlp_data.codes, dtype=np.uint8),)
-
-    def objgrad(self, x, gx=None, ys=None, gs=None, xk=None):
-        fx = C.c_double()
-        where = C.c_int32(0)
-        self._order(x, gx, ys, gs, xk)
-        rc = self._check(self._lib.fpsq_band_nlp_objgrad(self._h, self._q, _lib.ptr(x), self.sigma, self.rho, self.eta,
-                                                         self.delta, _lib.ptr(xk), C.byref(fx), _lib.ptr(gx), _lib.ptr(ys),
-                                                         _lib.ptr(gs), C.byref(where)))
-        if rc and where.value == -1:
-            import warnings
-            warnings.warn("DeviceBandSepFuncNLP: J(x) holds a non-finite value (nothing was factorised or evaluated)")
-            return float("nan"), rc
-        self.factorizations += 1
-        if rc:
-            import warnings
-            warnings.warn("DeviceBandSepFuncNLP: J J' + delta I is not positive definite (no valid factorisation)")
-            return float("nan"), rc
-        return fx.value, 0
 
 
 class DeviceArrowBandSepFuncNLP(DeviceBandSepFuncNLP):

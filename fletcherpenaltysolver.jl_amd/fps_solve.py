@@ -683,6 +683,17 @@ class _DevicePenalty:
         return {"objgrad_calls": self.nobjgrad, "hprod_calls": self.nhprod}
 
 
+# the function table of include/fpsq.h (FPSQ_FN_*) on torch tensors: code -> (psi, psi', psi''), as problems.FN_TABLE has it
+_TORCH_FN = (
+    (lambda t, x: 0.5 * x * x, lambda t, x: x, lambda t, x: t.ones_like(x)),
+    (lambda t, x: x * x * x / 6.0, lambda t, x: 0.5 * x * x, lambda t, x: x),
+    (lambda t, x: t.sin(x), lambda t, x: t.cos(x), lambda t, x: -t.sin(x)),
+    (lambda t, x: t.cos(x), lambda t, x: -t.sin(x), lambda t, x: -t.cos(x)),
+    (lambda t, x: t.exp(x), lambda t, x: t.exp(x), lambda t, x: t.exp(x)),
+    (lambda t, x: t.tanh(x), lambda t, x: 1.0 - t.tanh(x) ** 2, lambda t, x: -2.0 * t.tanh(x) * (1.0 - t.tanh(x) ** 2)),
+)
+
+
 class _DeviceNLPPenalty(_DevicePenalty):
     """The penalty function of a device-resident model with NONLINEAR constraints (DeviceBandSepQuadNLP, on an arrow band
     DeviceArrowBandSepQuadNLP; fpsq_band_nlp_*): the
@@ -693,6 +704,29 @@ class _DeviceNLPPenalty(_DevicePenalty):
     def __init__(self, dev, torch, hessian_approx=2):
         super().__init__(dev, torch, hessian_approx)
         self._x_at = None   # a clone of the x of the last objgrad
+        # function terms in the objective (dev.set_objective_terms): what the user's f and grad f gain, for the outer loop's
+        # scores -- per function code present, the indices of its entries with w_j != 0 and their weights, on the device
+        self._terms = []
+        w, codes = getattr(dev, "obj_w", None), getattr(dev, "obj_codes", None)
+        if w is not None:
+            for c in range(len(_TORCH_FN)):
+                idx = np.flatnonzero((codes == c) & (w != 0.0))
+                if idx.size:
+                    self._terms.append((c, torch.from_numpy(idx).to(self.q.device), torch.from_numpy(w[idx]).to(self.q.device)))
+
+    def _psi(self, x, order):
+        """w .* (the order-th derivative of psi at x), 0 where w_j = 0"""
+        out = self.torch.zeros_like(x)
+        for c, idx, wc in self._terms:
+            out[idx] = wc * _TORCH_FN[c][order](self.torch, x[idx])
+        return out
+
+    def state(self, x):
+        f, ncx, ys, ncx_inf = super().state(x)
+        return (f + float(self._psi(x, 0).sum()) if self._terms else f), ncx, ys, ncx_inf
+
+    def grad_f(self, x):
+        return super().grad_f(x) + self._psi(x, 1) if self._terms else super().grad_f(x)
 
     def objgrad_(self, x, g):
         fx, g = super().objgrad_(x, g)

@@ -119,6 +119,7 @@ end
 # Direct back-end for sparse banded Jacobians: the role of LDLtSolver (src/solve_two_systems_struct.jl:299-353,
 # src/solve_linear_system.jl:142-252) on the MI355X -- include/fpsq.h, fpsq_band_*.  Same seam, same keyword names
 # (ldlt_tol, ldlt_r1, ldlt_r2).     FletcherPenaltySolver.qdsolver_correspondence[:hip_ldlt] = HIPLDLtSolver
+# (The device-resident models fpsq_band_nlp_* are not wrapped here; fpsq_band_nlp_set_objective_terms(b, nlp, w, codes) adds w_j psi(x_j) to their objective: include/fpsq.h.)
 
 struct FpsqBandInfo
   n::Int64; m::Int64; nnz::Int64; nblocks::Int64; bandwidth_blocks::Int64; factor_bytes::Int64

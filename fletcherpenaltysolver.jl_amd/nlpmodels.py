@@ -289,6 +289,26 @@ class SepQuadConModel(EqQPModel):
 
         return sp.csr_matrix((self.jac_coord(x), self.qp.colind, self.qp.rowptr), shape=(self.qp.m, self.qp.n))
 
+    # function terms in the objective (problems.with_objective_terms: data.obj_w, data.obj_codes), here and in the subclasses:
+    # f gains sum_j w_j psi(x_j), grad f gains w psi'(x), Hess f = diag(q_x) with q_x = q + w psi''(x).  Without them every
+    # method computes what the class computed before
+    def _obj_terms(self, x, order):
+        from .problems import objective_terms
+
+        return objective_terms(self.data, x, order)
+
+    def _qx(self, x):
+        t = self._obj_terms(x, 2)
+        return self.qp.qdiag if t is None else self.qp.qdiag + t
+
+    def obj(self, x):
+        t = self._obj_terms(x, 0)
+        return super().obj(x) if t is None else super().obj(x) + float(t.sum())
+
+    def grad(self, x):
+        t = self._obj_terms(x, 1)
+        return super().grad(x) if t is None else super().grad(x) + t
+
     def cons(self, x):
         x = np.asarray(x, float)
         return self._A @ x + 0.5 * (self._H @ (x * x)) - self.b
@@ -298,7 +318,7 @@ class SepQuadConModel(EqQPModel):
     def jtprod(self, x, v): return self._J(x).T @ v
 
     def hprod(self, x, y, v, obj_weight=1.0):
-        return obj_weight * self.qp.qdiag * np.asarray(v) + (self._H.T @ y) * np.asarray(v)
+        return obj_weight * self._qx(x) * np.asarray(v) + (self._H.T @ y) * np.asarray(v)
 
     def ghjvprod(self, x, g, v): return self._H @ (np.asarray(g) * np.asarray(v))
 
@@ -332,7 +352,7 @@ class SepFuncConModel(SepQuadConModel):
         return self.qp.vals + self.hvals * fn_apply(self.codes, np.asarray(x, float)[self.qp.colind], 1)
 
     def hprod(self, x, y, v, obj_weight=1.0):
-        return obj_weight * self.qp.qdiag * np.asarray(v) + (self._at(x, 2).T @ y) * np.asarray(v)
+        return obj_weight * self._qx(x) * np.asarray(v) + (self._at(x, 2).T @ y) * np.asarray(v)
 
     def ghjvprod(self, x, g, v): return self._at(x, 2) @ (np.asarray(g) * np.asarray(v))
 

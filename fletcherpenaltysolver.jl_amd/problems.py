@@ -319,6 +319,51 @@ def pendulum_like(N=2000, tau=0.05, alpha=0.1, seed=1234) -> SepFuncNLP:
     return _sepfunc(qp, hvals, codes)
 
 
+def with_objective_terms(data, w, codes=None):
+    """A copy of a SepQuadNLP, SepFuncNLP or CoupledQuadNLP with ELEMENTWISE FUNCTION TERMS IN THE OBJECTIVE:
+    f(x) = 1/2 x' diag(q) x + d'x + sum_j w_j psi_kj(x_j), psi from FN_TABLE by one code byte per VARIABLE (`codes`, default
+    every code 0); an entry with w_j = 0 contributes nothing and is not evaluated.  The copy carries `obj_w` (float64, n) and
+    `obj_codes` (uint8, n) (nlpmodels' host classes and DeviceBandSepQuadNLP honour them; include/fpsq.h
+    fpsq_band_nlp_set_objective_terms); without this function the attributes are absent.  The constraints, b among them, stay."""
+    import copy
+
+    n = data.qp.n
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    codes = np.zeros(n, dtype=np.uint8) if codes is None else np.ascontiguousarray(codes, dtype=np.uint8)
+    assert w.shape == (n,) and codes.shape == (n,)
+    assert not np.any(codes[w != 0.0] >= len(FN_TABLE)), "a function code outside the table under a weight that is not 0"
+    out = copy.copy(data)
+    out.obj_w, out.obj_codes = w, codes
+    return out
+
+
+def objective_terms(data, x, order):
+    """w_j times the order-th derivative (0, 1, 2) of psi_kj at x_j for the terms of `with_objective_terms`, entry by entry
+    (0 where w_j = 0, whatever x_j), or None when `data` carries none"""
+    w = getattr(data, "obj_w", None)
+    if w is None:
+        return None
+    x = np.asarray(x, float)
+    out = np.zeros_like(x)
+    on = w != 0.0
+    if on.any():
+        out[on] = w[on] * fn_apply(data.obj_codes[on], x[on], order)
+    return out
+
+
+def pendulum_energy_like(N=2000, beta=0.5, gamma=0.05, **kwargs) -> SepFuncNLP:
+    """`pendulum_like(N)` with the potential energy -beta cos theta_k on every theta (k = 0 .. N) and the control cost
+    gamma exp(u_k) on every control in the objective: a problem whose objective is no diagonal QP."""
+    data = pendulum_like(N, **kwargs)
+    n = data.qp.n
+    idx = np.arange(n)
+    w, codes = np.zeros(n), np.zeros(n, dtype=np.uint8)
+    theta, ctrl = idx % 3 == 0, (idx % 3 == 2) & (idx < 3 * N)
+    w[theta], codes[theta] = -beta, FN_COS
+    w[ctrl], codes[ctrl] = gamma, FN_EXP
+    return with_objective_terms(data, w, codes)
+
+
 @dataclass
 class CoupledQuadNLP(SepQuadNLP):
     """A SepQuadNLP plus coupling terms t = (t_row, t_j, t_k, t_w), each adding t_w x_tj x_tk to c_trow (0-based, t_j != t_k):

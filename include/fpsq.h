@@ -677,6 +677,32 @@ int fpsq_band_set_input_stream(fpsq_band b, int32_t enabled, void *hip_stream);
  *                         returns the soft code 1 with *fx = nan, *info = -1 (no pivot row), nothing factorised, nothing
  *                         evaluated and no output written -- what a failed factorisation returns, and the state an hprod
  *                         refuses.  Function terms TOGETHER with coupling terms are not offered.
+ *   fpsq_band_nlp_set_objective_terms  ELEMENTWISE FUNCTION TERMS IN THE OBJECTIVE of a model made by ANY of the five create
+ *                         entries: one weight w_j and one code byte per VARIABLE (n doubles, n bytes; host or device pointers,
+ *                         copied; codes NULL: every code 0) name psi from the same table, and
+ *                           f(x) = 1/2 x' diag(q) x + d'x + sum_j w_j psi_kj(x_j),
+ *                           grad f = q .* x + d + w .* psi'(x),     Hess f = diag(q_x),  q_x = q + w .* psi''(x):
+ *                         a pendulum's potential energy sum (1 - cos theta_k), an exponential control cost, a saturating tanh
+ *                         tracking term, a cubic regulariser.  The constraints, J(x), the pattern and the factorisation are
+ *                         untouched.  In the formulas of fpsq_band_nlp_objgrad / _hprod above, g is grad f(x) and every q is q_x:
+ *                         qe = q_x - H'ys (with coupling terms E = diag(q_x - H'ys) - Wo(ys)), and f gains sum_j w_j psi(x_j).
+ *                         An entry with w_j = 0 contributes exactly nothing and is NOT evaluated (exp at x_j = 800 under
+ *                         w_j = 0 is harmless, and its code byte may hold anything); a code >= 6 under w_j != 0 gives
+ *                         FPSQ_ERR_ARG and a message that names the first such j; a model of another handle: FPSQ_ERR_ARG.
+ *                         w NULL REMOVES the terms: the model is then the one it was before, with the same launches and the
+ *                         same bits.  The call may come at any time and any number of times; it clears the model's point, so
+ *                         an hprod after it gives FPSQ_ERR_STATE ("no successful objgrad") until the next objgrad.  An objgrad
+ *                         with terms adds ONE elementwise launch behind the value launches of J(x) and before the factorisation:
+ *                         it rewrites the effective vectors q_x and d_e = d + w .* (psi'(x) - psi''(x) .* x) -- so that
+ *                         q_x .* x + d_e = grad f(x) and the kernels that take (q, d) take (q_x, d_e) unchanged -- and sums f in
+ *                         a fixed order into one partial per workgroup (no atomics on doubles), from which *fx is finished.
+ *                         A Hessian product and fpsq_band_nlp_cons add none: they run on what the objgrad left.  NON-FINITE
+ *                         OBJECTIVE: a non-finite w_j psi, w_j psi' or w_j psi'' raises the word a non-finite J(x) raises, read
+ *                         once per objgrad BEFORE it factorises (a model with both kinds of terms reads once); the objgrad
+ *                         returns what fpsq_band_nlp_create_fn describes -- soft code 1, *fx = nan, *info = -1, nothing
+ *                         factorised or evaluated, no output written, the word cleared -- and the message says whether J(x),
+ *                         the objective or both raised it.  Memory with terms: 3 n doubles (w, q_x, d_e), n code bytes and
+ *                         one double per workgroup of the A-side grid; it stays with the model after the terms are removed.
  * Destroy a model before the handle it was created on. */
 enum { /* phi, phi', phi'' of a function code (one byte per entry) */
   FPSQ_FN_HALFSQ = 0, /* 1/2 x^2,  x,         1                  */
@@ -702,6 +728,7 @@ int fpsq_band_nlp_create_coupled_arrow(fpsq_band b, const double *qdiag, const d
                                        const double *a_vals, const double *h_vals,
                                        int64_t nterms, const int32_t *t_row, const int32_t *t_j, const int32_t *t_k,
                                        const double *t_w, fpsq_band_nlp *out);
+int fpsq_band_nlp_set_objective_terms(fpsq_band b, fpsq_band_nlp nlp, const double *w, const uint8_t *codes);
 int fpsq_band_nlp_destroy(fpsq_band_nlp nlp);
 int fpsq_band_nlp_objgrad(fpsq_band b, fpsq_band_nlp nlp, const double *x, double sigma, double rho, double eta, double delta,
                           const double *xk, double *fx, double *gx, double *ys, double *gs, int32_t *info);

@@ -10,6 +10,12 @@ pattern, a and h (fpsq_band_nlp_create_arrow), everything in HBM:
    python tools/band_fn_nlp.py --shape pendulum --only fn      # one side, in this process (also the run for a kernel trace)
    python tools/band_fn_nlp.py --shape pendulum --pairs 5      # both sides in fresh child processes, interleaved
    python tools/band_fn_nlp.py --accuracy                      # the error table of tests/test_gpu_band_fn_nlp.py, every case
+   python tools/band_fn_nlp.py --shape pendulum --only fn --objective-terms   # the same model WITHOUT and WITH function terms in
+                                                               # the objective (fpsq_band_nlp_set_objective_terms), alternating on
+                                                               # ONE handle: what k_bn_objfn and the effective vectors cost
+   python tools/band_fn_nlp.py --shape aug2dc --only separable --pairs 5 --other-lib <another libfpsq.so>
+                                                               # one side on this build and on another (FPSQ_LIB_PATH), interleaved
+                                                               # fresh processes: an unchanged path against the build before
 ONE SIDE PER PROCESS, as tools/band_nlp.py explains (a second band handle in a process factorises slower).  Shapes:
 aug2dc = aug2dc_like(N=100) with 2 mean rows and 16 parameter columns (the arrow shape of profiles/band_coupled_arrow_nlp.md),
 headline = pde_control_like(n=1e6, m=1e5) with 3 mean rows and 5 parameter columns,
@@ -40,32 +46,48 @@ ap.add_argument("--only", default="fn", choices=["fn", "separable"], help="the s
 ap.add_argument("--pairs", type=int, default=0)
 ap.add_argument("--accuracy", action="store_true")
 ap.add_argument("--json", action="store_true", help="(child of --pairs) print one JSON line")
+ap.add_argument("--objective-terms", action="store_true",
+                help="time the side of --only without and with function terms in the objective, alternating on one handle")
+ap.add_argument("--other-lib", default=None, help="(with --pairs) the side of --only on this build against another build")
 args = ap.parse_args()
 
 if args.pairs:   # this process never opens the GPU: every measurement is a fresh child
     rows = []
+    sides = (("other", args.only, args.other_lib), ("this", args.only, None)) if args.other_lib else \
+        (("separable", "separable", None), ("fn", "fn", None))
     for p in range(args.pairs):
         row = {}
-        for only in ("separable", "fn"):
+        for label, only, lib in sides:
+            env = dict(os.environ)
+            env.pop("FPSQ_LIB_PATH", None)
+            if lib:
+                env["FPSQ_LIB_PATH"] = os.path.abspath(lib)
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--shape", args.shape, "--json", "--evals",
                                   str(args.evals), "--warmup", str(args.warmup), "--repeats", str(args.repeats), "--only", only],
-                                 check=True, capture_output=True, text=True, timeout=900).stdout
-            row.update({f"{only} {k}": v for k, v in json.loads(out.strip().splitlines()[-1]).items()})
+                                 check=True, capture_output=True, text=True, timeout=900, env=env).stdout
+            row.update({f"{label} {k}": v for k, v in json.loads(out.strip().splitlines()[-1]).items()})
         rows.append(row)
         print(f"pair {p}: " + ", ".join(f"{k} {v:.4f}" for k, v in row.items()), flush=True)
     med = {k: float(np.median([r[k] for r in rows])) for k in rows[0]}
     spread = {k: max(r[k] for r in rows) - min(r[k] for r in rows) for k in rows[0]}
     for k in rows[0]:
         print(f"{k}: median {med[k]:.4f} ms (spread {spread[k]:.4f})")
+    a, b = sides[1][0], sides[0][0]
     for k in ("objgrad", "hprod 2", "hprod 1"):
-        print(f"fn {k} - separable {k} = {med['fn ' + k] - med['separable ' + k]:+.4f} ms "
-              f"(x {med['fn ' + k] / med['separable ' + k]:.3f}; the separable side's spread {spread['separable ' + k]:.4f})")
+        print(f"{a} {k} - {b} {k} = {med[a + ' ' + k] - med[b + ' ' + k]:+.4f} ms "
+              f"(x {med[a + ' ' + k] / med[b + ' ' + k]:.3f}; the {b} side's spread {spread[b + ' ' + k]:.4f})")
     sys.exit(0)
 
 import torch  # noqa: E402
 
 import fps_amd  # noqa: E402,F401
-from fps_amd import problems  # noqa: E402
+from fps_amd import _lib, problems  # noqa: E402
+
+if os.environ.get("FPSQ_LIB_PATH"):   # another build may predate entries this tree declares: bind the ones it has
+    import ctypes
+
+    _have = ctypes.CDLL(_lib.LIB_PATH)
+    _lib.SYMBOLS = [s for s in _lib.SYMBOLS if hasattr(_have, s[0])]
 from fps_amd.device_qp import DeviceArrowBandSepFuncNLP, DeviceArrowBandSepQuadNLP, DeviceBandSepFuncNLP  # noqa: E402
 
 if args.accuracy:
@@ -148,6 +170,34 @@ def timed(fn):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / args.evals
 
+
+if args.objective_terms:
+    # the draw of tests/objfn_cases.py: codes uniform over the table, |w| in [0.5, 1.5), a quarter of the weights 0
+    from objfn_cases import terms
+
+    w, codes = terms(qp.n)
+    if args.shape == "pendulum":   # (theta of a rotating pendulum grows without bound: its energy terms, not a draw with exp)
+        energy = problems.pendulum_energy_like(N=100_000)
+        w, codes = energy.obj_w, energy.obj_codes
+    else:                          # exp stays in double range at every point that is evaluated
+        big = np.max(np.abs(np.stack([qp.point(k) for k in range(8)])), axis=0) > 30.0
+        codes[big & (codes == problems.FN_EXP)] = problems.FN_SIN
+    w, codes = t(w), t(codes)
+    both = {f"{k} {side}": [] for k in fns for side in ("plain", "terms")}
+    for r in range(args.repeats):
+        for side in ("plain", "terms"):
+            dev.set_objective_terms(w if side == "terms" else None, codes if side == "terms" else None)
+            objgrad(xs[0])
+            for k, fn in fns.items():
+                both[f"{k} {side}"].append(timed(fn))
+    print(f"{qp.name} ({args.only}): n={qp.n} m={qp.m} nnz={qp.nnz}; {args.evals} evaluations after {args.warmup}, "
+          f"{args.repeats} repeats, without and with objective terms alternating on one handle")
+    for k in fns:
+        a, b = both[f"{k} plain"], both[f"{k} terms"]
+        print(f"{k}: plain median {np.median(a):.4f} ms (spread {max(a) - min(a):.4f}), with terms {np.median(b):.4f} ms "
+              f"(spread {max(b) - min(b):.4f}), difference {np.median(b) - np.median(a):+.4f} ms")
+    dev.close()
+    sys.exit(0)
 
 res = {k: [] for k in fns}
 split = {}

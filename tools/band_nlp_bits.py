@@ -20,6 +20,11 @@ and the bits of fx.  A line belongs to one evaluation, so a differing line names
   fn          DeviceBandSepFuncNLP        the function model (tests/sepfunc_ref.py fn_data) on every case of
                                           tests/lane_group_cases.py, and DeviceArrowBandSepFuncNLP on the arrow shapes.  NOT among
                                           the defaults: a build from before fpsq_band_nlp_create_fn lacks the entry
+  objfn       DeviceBandSepFuncNLP        the function model with function terms in the OBJECTIVE (tests/objfn_cases.py
+                                          objfn_data: fpsq_band_nlp_set_objective_terms) on every case of tests/lane_group_cases.py,
+                                          and DeviceArrowBandSepQuadNLP / DeviceArrowBandCoupledQuadNLP with the same draw on the
+                                          643-row arrow shape.  NOT among the defaults: a build from before the entry lacks it
+                                          (the entry is bound only when the build under FPSQ_LIB_PATH has it)
 Accuracy is the tests' business."""
 import argparse
 import hashlib
@@ -140,5 +145,17 @@ for model in args.models.split(","):
             border, cols = T.CASES[name][2]
             data = F.fn_data_of(T.CASES[name][0]()[0])
             evaluate(model, name, device_qp.DeviceArrowBandSepFuncNLP(data, border=border, cols=cols, **kw))
+    elif model == "objfn":
+        import coupled_arrow_cases as ca
+        import objfn_cases as oc
+        import test_gpu_band_arrow_nlp as T
+
+        for name in L.NAMES:
+            evaluate(model, name, device_qp.DeviceBandSepFuncNLP(oc.objfn_data(name), **kw))
+        border, cols = T.CASES[T.CASE_643][2]
+        evaluate(model, "arrow-" + T.CASE_643, DeviceArrowBandSepQuadNLP(oc.with_terms(T._problem(T.CASE_643)[1]), border=border,
+                                                                        cols=cols, **kw))
+        evaluate(model, "coupled-arrow-" + T.CASE_643, DeviceArrowBandCoupledQuadNLP(oc.with_terms(ca.problem(T.CASE_643)[0]),
+                                                                                border=border, cols=cols, **kw))
     else:
         raise SystemExit(f"unknown model {model}")
